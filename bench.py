@@ -11,16 +11,28 @@ instance range is regenerated locally from (seed, global id)) and the solved
 contact forces are all-gathered over RCCL/xGMI inside the timed step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
-                    [--horizon 10] [--gait trot] [--no-cpu-baseline] [--reduced]
+                    [--horizon 10] [--gait trot] [--reduced]
+                    [--dump-outputs DIR] [--full [--no-cpu-baseline] [--no-second-line]]
+
+A plain run does what the headline needs and nothing else: set up, a fixed
+clock pre-warm, W untimed and exactly K timed steps, one JSON line.
+`--dump-outputs DIR` then writes what the last timed step returned to its
+caller as DIR/<name>.npy (dump_outputs below); the inputs depend on the
+arguments alone, so two builds can be compared output for output.  `--full`
+adds every side measurement, each a run of its own before the headline's
+warm-up (the other formulation, the shuffled order, the persistent solver,
+the reference's weight sets, the PCIe-inclusive form) and the CPU baseline
+after it; `--no-second-line` / `--no-cpu-baseline` take those out again.
 
 The headline solves the reference's call as written: the literal
 12N-variable QP, every force an ADMM variable and the swing legs held by
 their fz in [0, 0] rows (spec.literal_full_qp = 1, A1RobotControl.cpp:557-578;
-N <= 10 on one wavefront through the wrench space).  At N=1
-the same line also carries `reduced_qp`: the same workload solved as the
-stance-only reduction (swing forces eliminated exactly: same optimum,
-different ADMM iterates), timed in the same run; `--reduced`
-makes the reduction the headline (then the second line is `literal_full_qp`).
+N <= 10 on one wavefront through the wrench space).  With
+`--full` at N=1 the same line also carries `reduced_qp`: the same workload
+solved as the stance-only reduction (swing forces eliminated exactly: same
+optimum, different ADMM iterates, DESIGN.md §3), timed in the same run;
+`--reduced` makes the reduction the headline (then the second line is
+`literal_full_qp`).
 
 Rank 0 prints ONE JSON line.  Launch for N>1 GPUs:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
@@ -40,6 +52,7 @@ sys.path.insert(0, ROOT)
 PEAK_FP32_TFLOPS = 157.3   # MI355X_MICROARCH.md: FP32 vector == FP32 MFMA peak
 PEAK_HBM_GBS = 8000.0      # MI355X HBM3E spec
 SEED = 20261015
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs: budget of all the files together
 
 
 def srbd_flops_alg(horizon, iters, rho_updates):
@@ -165,6 +178,31 @@ def _free_port():
     return port
 
 
+def dump_outputs(directory, arrays, max_bytes=DUMP_MAX_BYTES):
+    """--dump-outputs: write {name: array} as directory/<name>.npy, float32
+    (integer arrays too: status, iteration and rho-update counts are far below
+    2^24) or float64 where the array is float64, at most max_bytes of array
+    data in all.  Every array gets an equal share of the budget; one that
+    exceeds its share is cut to a sorted row sample drawn by numpy
+    default_rng(SEED + 2) from its row count alone, so the same arguments
+    keep the same rows in every build.  Returns {name: rows written}."""
+    os.makedirs(directory, exist_ok=True)
+    share = max_bytes // max(1, len(arrays))
+    rows = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        a = a.reshape(a.shape[0], -1) if a.ndim > 1 else a.reshape(-1)
+        row_bytes = a.itemsize * (a.shape[1] if a.ndim > 1 else 1)
+        keep = share // row_bytes
+        if a.shape[0] > keep:
+            pick = np.sort(np.random.default_rng(SEED + 2).choice(a.shape[0], size=keep, replace=False))
+            a = a[pick]
+        np.save(os.path.join(directory, name + ".npy"), a)
+        rows[name] = int(a.shape[0])
+    return rows
+
+
 def launch_ranks(n, argv):
     """`bench.py --gpus N` without a launcher: start N ranks through
     torch.distributed.run as a CHILD process (this process never touches the
@@ -220,14 +258,20 @@ def main():
     ap.add_argument("--batch", type=int, default=4096, help="instances per GPU")
     ap.add_argument("--horizon", type=int, default=10)
     ap.add_argument("--gait", default="trot")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (other formulation, shuffled order, "
+                         "persistent solver, reference weights, PCIe-inclusive) and the CPU "
+                         "baseline; off: the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--reduced", action="store_true",
                     help="headline = the stance-only reduction (literal_full_qp = 0) instead of "
                          "the reference's literal 12N-variable QP")
     ap.add_argument("--literal", action="store_true",
                     help="the literal QP as headline (the default; kept for old command lines)")
     ap.add_argument("--no-literal-line", "--no-second-line", dest="no_second_line",
-                    action="store_true", help="skip the other formulation's side measurement at N = 1")
+                    action="store_true", help="with --full: skip the side measurements before the headline")
     ap.add_argument("--literal-steps", "--second-steps", dest="second_steps", type=int, default=50)
     ap.add_argument("--prewarm", type=int, default=64,
                     help="untimed headline solves before everything else (GPU clock ramp)")
@@ -253,6 +297,10 @@ def main():
     args.literal = not args.reduced
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if not args.full:  # a plain run: the headline only
+        args.no_second_line = args.no_cpu_baseline = True
 
     if "WORLD_SIZE" not in os.environ:
         if args.gpus > 1:  # no launcher: spawn the ranks ourselves (before any GPU call)
@@ -359,11 +407,11 @@ def main():
     # solves (--prewarm, recorded in the line) runs first, whatever side
     # measurements the flags select, so the headline is timed at the clocks a
     # continuously running controller sees and does not move with the flag
-    # set.  Then the side measurements, then W untimed warm-up steps and
-    # exactly K timed steps.  Every rank runs the pre-warm and the two
-    # rank-local side lines (its own shard, no collective), so an N-GPU run
-    # times its headline at the same clocks as the 1-GPU run; the line
-    # printed is rank 0's.
+    # set.  Then the side measurements (--full only), then W untimed warm-up
+    # steps and exactly K timed steps.  Every rank runs the pre-warm and,
+    # with --full, the two rank-local side lines (its own shard, no
+    # collective), so an N-GPU run times its headline at the same clocks as
+    # the 1-GPU run; the line printed is rank 0's.
     for _ in range(args.prewarm):
         solver.solve(d_x0, d_xr, d_ft, d_ct, out=out, max_legs=legs, stream=stream.cuda_stream)
     torch.cuda.synchronize(dev)
@@ -433,6 +481,19 @@ def main():
     else:
         kern_ms = step_ms
         gather_ms = np.zeros(K)
+
+    if args.dump_outputs is not None and rank == 0:
+        # what step K - 1 handed its caller: the solver's result set (this
+        # rank's shard), and the whole batch's forces where they are gathered
+        if handle is not None:
+            last = {"u0_all": handle.u0_all}
+        else:
+            o = outs[(K - 1) % len(outs)]
+            last = {"u0": o.u0, "status": o.status, "iters": o.iters,
+                    "rho_updates": o.rho_updates, "obj": o.obj}
+            if gather is not None:
+                last["u0_all"] = gather[(K - 1) % len(gather)].out
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
 
     # per-instance stats of the solved batch (identical every step)
     if handle is not None:  # stats not gathered in the timed loop: one plain solve

@@ -44,6 +44,36 @@ def test_bench_rejects_world_size_mismatch():
     assert "WORLD_SIZE=2 but --gpus 4" in p.stderr
 
 
+def test_dump_outputs_formats_and_budget(tmp_path):
+    """--dump-outputs' writer: float32 / float64 .npy files, every array whole
+    under the budget, a fixed sorted row sample above it."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    arrays = {"u0": rng.standard_normal((100, 12)).astype(np.float32),
+              "iters": rng.integers(0, 4000, 100).astype(np.int32),
+              "obj64": rng.standard_normal(100)}
+    rows = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert rows == {"u0": 100, "iters": 100, "obj64": 100}
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in arrays}
+    assert got["u0"].dtype == np.float32 and got["iters"].dtype == np.float32
+    assert got["obj64"].dtype == np.float64
+    for k in arrays:
+        assert np.array_equal(got[k], arrays[k])
+    # 3 arrays, 2400 bytes: 800 each -> 16 rows of u0 (48 B), 100 of the others
+    budget = 2400
+    rows = bench.dump_outputs(str(tmp_path / "b"), arrays, max_bytes=budget)
+    assert rows == {"u0": 16, "iters": 100, "obj64": 100}
+    cut = np.load(str(tmp_path / "b" / "u0.npy"))
+    assert cut.shape == (16, 12)
+    idx = [int(np.flatnonzero((arrays["u0"] == r).all(axis=1))[0]) for r in cut]
+    assert idx == sorted(set(idx))
+    assert sum(np.load(str(tmp_path / "b" / (k + ".npy"))).nbytes for k in arrays) <= budget
+    bench.dump_outputs(str(tmp_path / "c"), arrays, max_bytes=budget)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "u0.npy")), cut)
+
+
 def test_usable_cores_and_cpu_model():
     sys.path.insert(0, ROOT)
     import bench

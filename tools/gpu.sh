@@ -7,7 +7,7 @@
 #   tests        pytest -m gpu (parity suite)            -> pytest_gpu.log
 #   tk=EXPR      pytest -m gpu -k EXPR                   -> pytest_k.log
 #   smoke        __graft_entry__.smoke()                 -> smoke.log
-#   bench        python bench.py (default line)          -> bench.json
+#   bench        python bench.py --full (every side line) -> bench.json
 #   ktrace       rocprofv3 --kernel-trace --stats of the bench -> kernel_stats.csv
 #   ktraceh      headline-only kernel trace (--no-second-line), last 50 launches -> kernel_stats_headline.csv
 #   sq[=VAR]     two SQ counter passes of perf_kernel.py VAR (default; env N, GAIT, LITERAL, TB = batch)
@@ -53,11 +53,11 @@ for step in "$@"; do
         || fail "$out/smoke.log"
       cat "$out/smoke.log" ;;
     bench)
-      timeout -k 10 300 python bench.py ${arg//:/ } > "$out/bench.json" 2> "$out/bench.err" || fail "$out/bench.err"
+      timeout -k 10 300 python bench.py --full ${arg//:/ } > "$out/bench.json" 2> "$out/bench.err" || fail "$out/bench.err"
       cat "$out/bench.json" ;;
     ktrace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$out/ktrace" -o run -- python bench.py --steps 50 --warmup 5 \
-        --no-cpu-baseline ${arg//:/ } > "$out/ktrace.log" 2>&1 || fail "$out/ktrace.log"
+        --full --no-cpu-baseline ${arg//:/ } > "$out/ktrace.log" 2>&1 || fail "$out/ktrace.log"
       python tools/db_kernel_stats.py "$out/ktrace" > "$out/kernel_stats.csv" && rm -rf "$out/ktrace"
       head -5 "$out/kernel_stats.csv" ;;
     ktraceh)
@@ -100,7 +100,7 @@ for step in "$@"; do
     configs)
       for spec in "16 trot 65536" "20 pace 65536" "10 mixed 131072"; do
         set -- $spec
-        timeout -k 10 240 python bench.py --horizon $1 --gait $2 --batch $3 --steps 20 --warmup 3 --no-cpu-baseline \
+        timeout -k 10 240 python bench.py --full --horizon $1 --gait $2 --batch $3 --steps 20 --warmup 3 --no-cpu-baseline \
           >> "$out/configs.jsonl" 2>> "$out/configs.err" || fail "$out/configs.err"
       done
       cat "$out/configs.jsonl" ;;
