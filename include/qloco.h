@@ -544,6 +544,85 @@ int qloco_mgpu_solve(qloco_mgpu *h, const qloco_srbd_spec *spec, const float *x0
 /* Releases the communicator and the buffers (NULL is a no-op). */
 int qloco_mgpu_destroy(qloco_mgpu *h);
 
+/* ====================================================================== */
+/* 11. A1 leg kinematics, batched (fp64)                                   */
+/*    replaces the per-leg block of GazeboA1ROS::gt_pose_callback          */
+/*    (unitree_ros/a1_cpp_open_source/src/GazeboA1ROS.cpp:306-331):        */
+/*    A1Kinematics::fk / jac (legKinematics/A1Kinematics.cpp:39-130),      */
+/*    foot_vel_rel = J qdot, root_quat.toRotationMatrix(),                 */
+/*    Utils::quat_to_euler (utils/Utils.cpp:7-33, asin clamp included),    */
+/*    the yaw-only root_rot_mat_z and the body / world frame copies.       */
+/* ====================================================================== */
+typedef struct qloco_a1_kin_params {
+  double rho_fix[4][5]; /* per leg: leg_offset_x, leg_offset_y, motor_offset, upper, lower */
+                        /* (GazeboA1ROS.cpp:79-101)                                        */
+  double rho_opt[4][3]; /* 0 (:98-99)                                                      */
+} qloco_a1_kin_params;
+void qloco_a1_kin_params_default(qloco_a1_kin_params *p);
+/* Device pointers, double, legs FL, FR, RL, RR.  Inputs: joint_pos[B*12],
+ * joint_vel[B*12], root_quat[B*4] as (w, x, y, z); root_pos[B*3] and
+ * root_lin_vel[B*3] optional (needed by foot_pos_world / foot_vel_world).
+ * Outputs, all optional (NULL) except foot_pos_rel: foot_pos_rel[B*12] (3x4
+ * col-major), j_foot[B*36] (the four 3x3 diagonal blocks of j_foot, each
+ * col-major), foot_vel_rel[B*12], root_rot_mat[B*9], root_euler[B*3],
+ * root_rot_mat_z[B*9] (3x3 col-major), foot_pos_abs / foot_vel_abs /
+ * foot_pos_world / foot_vel_world [B*12].  With a row stride of
+ * QLOCO_A1_STATE_LEN the outputs are the [6:9], [24:33], [33:42] and [42:54]
+ * fields of the section 9 record; this entry point writes dense arrays. */
+int qloco_a1_leg_kin(const qloco_a1_kin_params *prm, int64_t batch, const double *joint_pos,
+                     const double *joint_vel, const double *root_quat, const double *root_pos,
+                     const double *root_lin_vel, double *foot_pos_rel, double *j_foot,
+                     double *foot_vel_rel, double *root_rot_mat, double *root_euler,
+                     double *root_rot_mat_z, double *foot_pos_abs, double *foot_vel_abs,
+                     double *foot_pos_world, double *foot_vel_world, void *stream);
+
+/* ====================================================================== */
+/* 12. A1 state estimator, batched (fp64)                                  */
+/*    replaces A1BasicEKF (unitree_ros/a1_cpp_open_source/src/             */
+/*    A1BasicEKF.h:16-72, A1BasicEKF.cpp:7-164) as GazeboA1ROS::main_update */
+/*    calls it (GazeboA1ROS.cpp:204-209): init_state on the first tick,     */
+/*    update_estimation afterwards; 18 states (pos, vel, four feet), 28     */
+/*    measurements.  S is factored once (Cholesky) where the reference      */
+/*    solves twice with fullPivHouseholderQr; results agree to rounding.    */
+/* ====================================================================== */
+typedef struct qloco_a1_ekf_params {
+  double process_noise_pimu, process_noise_vimu, process_noise_pfoot; /* A1BasicEKF.h:16-18 */
+  double sensor_noise_pimu_rel_foot, sensor_noise_vimu_rel_foot;      /* :19-20 */
+  double sensor_noise_zfoot;                                          /* :21 */
+  int32_t assume_flat_ground; /* 1: the default-constructed member (GazeboA1ROS.h:160) */
+  int32_t reserved[7];
+} qloco_a1_ekf_params;
+void qloco_a1_ekf_params_default(qloco_a1_ekf_params *p);
+/* The filter state (x, P) of every robot lives in a device workspace of
+ * qloco_a1_ekf_workspace_bytes(batch) bytes (-1 for batch <= 0):
+ * QLOCO_A1_EKF_WS doubles per robot = x[18] | P, packed lower triangle, row
+ * by row [171] | pad. */
+#define QLOCO_A1_EKF_WS 192
+#define QLOCO_A1_EKF_STATE 18
+#define QLOCO_A1_EKF_MEAS 28
+int64_t qloco_a1_ekf_workspace_bytes(int64_t batch);
+/* init_state (A1BasicEKF.cpp:55-68): P = 3 I, x = (0, 0, 0.09, 0.., R fk_i + pos). */
+int qloco_a1_ekf_init(const qloco_a1_ekf_params *prm, int64_t batch, void *workspace,
+                      const double *root_rot_mat, const double *foot_pos_rel, void *stream);
+/* update_estimation (A1BasicEKF.cpp:70-164), one tick of every robot.
+ * Device pointers: dt[B], movement_mode[B] (int32), root_rot_mat[B*9] (3x3
+ * col-major), imu_acc[B*3], imu_ang_vel[B*3], foot_pos_rel[B*12],
+ * foot_vel_rel[B*12] (3x4 col-major), foot_force[B*4].  Outputs:
+ * root_pos[B*3] = x[0:3] and root_lin_vel[B*3] = x[3:6] required;
+ * estimated_contacts[B*4] (uint8) optional. */
+int qloco_a1_ekf_update(const qloco_a1_ekf_params *prm, int64_t batch, void *workspace,
+                        const double *dt, const int32_t *movement_mode,
+                        const double *root_rot_mat, const double *imu_acc,
+                        const double *imu_ang_vel, const double *foot_pos_rel,
+                        const double *foot_vel_rel, const double *foot_force, double *root_pos,
+                        double *root_lin_vel, uint8_t *estimated_contacts, void *stream);
+/* Dense x[B*18] and P[B*324] (18x18 col-major) out of / into the workspace
+ * (tests, logging, checkpoints).  set_state reads P's lower triangle. */
+int qloco_a1_ekf_get_state(int64_t batch, const void *workspace, double *x, double *P,
+                           void *stream);
+int qloco_a1_ekf_set_state(int64_t batch, void *workspace, const double *x, const double *P,
+                           void *stream);
+
 #ifdef __cplusplus
 }
 #endif

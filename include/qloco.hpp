@@ -18,6 +18,8 @@
  *                                    (PRMPCClass.h:69-71; gait_fast.cpp:620)
  *   ConvexMpcBatch                <- A1RobotControl::compute_grf MPC branch +
  *                                    ConvexMpc (A1RobotControl.cpp:452-600)
+ *   A1BasicEKFBatch               <- A1BasicEKF (a1_cpp_open_source/src/A1BasicEKF.h:25-72;
+ *                                    GazeboA1ROS.cpp:204-209)
  *   Kinematicclass                <- go1_rt_control Kinematicclass
  *                                    (Kinematics.h:30-61; servo.cpp:734-741, :1038-1051)
  *   ServoForceBlock               <- the go1 servo loop's force block (servo.cpp:1052-1243)
@@ -283,6 +285,45 @@ class A1QpBatch {
   int32_t *d_st_, *d_it_;
 };
 
+// ------------------------------------------------------------------------
+// A1BasicEKF (A1BasicEKF.h:25-72) over B robots, as GazeboA1ROS::main_update
+// drives it (GazeboA1ROS.cpp:204-209): init_state on the first tick,
+// update_estimation afterwards.  A1EstState carries the A1CtrlStates fields
+// the filter reads (movement_mode .. foot_force) and writes (estimated_* and
+// root_pos / root_lin_vel); x and P stay on the device (qloco_a1_ekf_*).
+struct A1EstState {
+  int movement_mode;
+  double root_rot_mat[9];                   // 3x3 col-major
+  double imu_acc[3], imu_ang_vel[3];
+  double foot_pos_rel[12], foot_vel_rel[12];  // 3x4 col-major, legs FL, FR, RL, RR
+  double foot_force[4];
+  bool estimated_contacts[4];
+  double estimated_root_pos[3], estimated_root_vel[3];
+  double root_pos[3], root_lin_vel[3];
+};
+
+class A1BasicEKFBatch {
+ public:
+  A1BasicEKFBatch(int batch, const qloco_a1_ekf_params *params = nullptr);
+  A1BasicEKFBatch(int batch, bool assume_flat_ground);
+  bool is_inited() const { return filter_initialized_; }
+  void init_state(const A1EstState *states);
+  void update_estimation(A1EstState *states, double dt);
+  // dense x (B * 18) and P (B * 324, col-major) of every filter
+  void get_state(double *x, double *P);
+  qloco_a1_ekf_params params;
+  int batch() const { return batch_; }
+
+ private:
+  int batch_;
+  bool filter_initialized_ = false;
+  DeviceArena arena_;
+  void *d_ws_;
+  double *d_in_, *d_out_;
+  int32_t *d_mode_;
+  uint8_t *d_ct_;
+  void stage(const A1EstState *states, double dt);
+};
 
 // ------------------------------------------------------------------------
 // Kinematicclass (go1_rt_control/src/kinematics/Kinematics.h:30-61).  The

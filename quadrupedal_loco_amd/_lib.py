@@ -51,6 +51,19 @@ class A1Params(C.Structure):
                 ("adaptive_rho_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class A1KinParams(C.Structure):
+    """Mirror of `qloco_a1_kin_params`."""
+    _fields_ = [("rho_fix", (C.c_double * 5) * 4), ("rho_opt", (C.c_double * 3) * 4)]
+
+
+class A1EkfParams(C.Structure):
+    """Mirror of `qloco_a1_ekf_params`."""
+    _fields_ = [("process_noise_pimu", C.c_double), ("process_noise_vimu", C.c_double),
+                ("process_noise_pfoot", C.c_double), ("sensor_noise_pimu_rel_foot", C.c_double),
+                ("sensor_noise_vimu_rel_foot", C.c_double), ("sensor_noise_zfoot", C.c_double),
+                ("assume_flat_ground", C.c_int32), ("reserved", C.c_int32 * 7)]
+
+
 vp = C.c_void_p
 i64 = C.c_int64
 i32 = C.c_int32
@@ -101,6 +114,14 @@ SIGNATURES = {
     "qloco_support_phase": (C.c_int, [i64] + [vp] * 8),
     "qloco_a1_params_default": (None, [C.POINTER(A1Params)]),
     "qloco_a1_qp_solve": (C.c_int, [C.POINTER(A1Params), i64] + [vp] * 9),
+    "qloco_a1_kin_params_default": (None, [C.POINTER(A1KinParams)]),
+    "qloco_a1_leg_kin": (C.c_int, [C.POINTER(A1KinParams), i64] + [vp] * 16),
+    "qloco_a1_ekf_params_default": (None, [C.POINTER(A1EkfParams)]),
+    "qloco_a1_ekf_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_a1_ekf_init": (C.c_int, [C.POINTER(A1EkfParams), i64, vp, vp, vp, vp]),
+    "qloco_a1_ekf_update": (C.c_int, [C.POINTER(A1EkfParams), i64] + [vp] * 13),
+    "qloco_a1_ekf_get_state": (C.c_int, [i64, vp, vp, vp, vp]),
+    "qloco_a1_ekf_set_state": (C.c_int, [i64, vp, vp, vp, vp]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),
     "qloco_mgpu_gather_rows": (C.c_int, [i64, i32, i32, vp]),
     "qloco_mgpu_reorder": (C.c_int, [i64, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -613,6 +613,98 @@ void A1QpBatch::compute_grf(const A1QpState *s, double *forces) {
 }
 
 
+// ---------------------------------------------------------------- A1BasicEKFBatch
+// device staging, doubles per robot: dt 1 | root_rot_mat 9 | imu_acc 3 |
+// imu_ang_vel 3 | foot_pos_rel 12 | foot_vel_rel 12 | foot_force 4 (= 44,
+// field-major); outputs root_pos 3 | root_lin_vel 3, then x 18 | P 324
+A1BasicEKFBatch::A1BasicEKFBatch(int batch, const qloco_a1_ekf_params *p)
+    : batch_(positive_batch(batch, "A1BasicEKFBatch")) {
+  if (p) params = *p;
+  else qloco_a1_ekf_params_default(&params);
+  const size_t B = batch;
+  const int64_t ws = qloco_a1_ekf_workspace_bytes(batch);
+  if (ws < 0) throw Error("qloco_a1_ekf_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_in_ = dalloc<double>(arena_, B * 44);
+  d_out_ = dalloc<double>(arena_, B * (6 + 18 + 324));
+  d_mode_ = dalloc<int32_t>(arena_, B);
+  d_ct_ = dalloc<uint8_t>(arena_, B * 4);
+}
+
+A1BasicEKFBatch::A1BasicEKFBatch(int batch, bool assume_flat_ground)
+    : A1BasicEKFBatch(batch, nullptr) {
+  params.assume_flat_ground = assume_flat_ground ? 1 : 0;
+}
+
+void A1BasicEKFBatch::stage(const A1EstState *s, double dt) {
+  const size_t B = batch_;
+  std::vector<double> in(B * 44);
+  std::vector<int32_t> mode(B);
+  double *pdt = in.data(), *rot = pdt + B, *acc = rot + 9 * B, *om = acc + 3 * B,
+         *fk = om + 3 * B, *fv = fk + 12 * B, *ff = fv + 12 * B;
+  for (size_t b = 0; b < B; ++b) {
+    pdt[b] = dt;
+    mode[b] = s[b].movement_mode;
+    for (int k = 0; k < 9; ++k) rot[9 * b + k] = s[b].root_rot_mat[k];
+    for (int k = 0; k < 3; ++k) {
+      acc[3 * b + k] = s[b].imu_acc[k];
+      om[3 * b + k] = s[b].imu_ang_vel[k];
+    }
+    for (int k = 0; k < 12; ++k) {
+      fk[12 * b + k] = s[b].foot_pos_rel[k];
+      fv[12 * b + k] = s[b].foot_vel_rel[k];
+    }
+    for (int k = 0; k < 4; ++k) ff[4 * b + k] = s[b].foot_force[k];
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  arena_.upload(d_mode_, mode.data(), sizeof(int32_t) * B);
+  arena_.sync();  // the host vectors go out of scope
+}
+
+void A1BasicEKFBatch::init_state(const A1EstState *s) {
+  if (!s) throw Error("A1BasicEKFBatch::init_state: null states", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  stage(s, 0.0);
+  abi_ok(qloco_a1_ekf_init(&params, batch_, d_ws_, d_in_ + B, d_in_ + 16 * B, arena_.stream()),
+         "qloco_a1_ekf_init");
+  arena_.sync();
+  filter_initialized_ = true;
+}
+
+void A1BasicEKFBatch::update_estimation(A1EstState *s, double dt) {
+  if (!s) throw Error("A1BasicEKFBatch::update_estimation: null states", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  stage(s, dt);
+  double *in = d_in_;
+  abi_ok(qloco_a1_ekf_update(&params, batch_, d_ws_, in, d_mode_, in + B, in + 10 * B, in + 13 * B,
+                             in + 16 * B, in + 28 * B, in + 40 * B, d_out_, d_out_ + 3 * B, d_ct_,
+                             arena_.stream()),
+         "qloco_a1_ekf_update");
+  std::vector<double> out(B * 6);
+  std::vector<uint8_t> ct(B * 4);
+  arena_.download(out.data(), d_out_, sizeof(double) * B * 6);
+  arena_.download(ct.data(), d_ct_, B * 4);
+  arena_.sync();
+  for (size_t b = 0; b < B; ++b) {  // A1BasicEKF.cpp:151-163
+    for (int l = 0; l < 4; ++l) s[b].estimated_contacts[l] = ct[4 * b + l] != 0;
+    for (int k = 0; k < 3; ++k) {
+      s[b].estimated_root_pos[k] = s[b].root_pos[k] = out[3 * b + k];
+      s[b].estimated_root_vel[k] = s[b].root_lin_vel[k] = out[3 * B + 3 * b + k];
+    }
+  }
+}
+
+void A1BasicEKFBatch::get_state(double *x, double *P) {
+  if (!x || !P) throw Error("A1BasicEKFBatch::get_state: null output", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  double *dx = d_out_ + 6 * B, *dP = dx + 18 * B;
+  abi_ok(qloco_a1_ekf_get_state(batch_, d_ws_, dx, dP, arena_.stream()), "qloco_a1_ekf_get_state");
+  arena_.download(x, dx, sizeof(double) * B * 18);
+  arena_.download(P, dP, sizeof(double) * B * 324);
+  arena_.sync();
+}
+
+
 // ------------------------------------------------------------------------
 // Kinematicclass -> qloco_leg_fk / qloco_leg_ik
 Kinematicclass::Kinematicclass(int max_legs) : cap_(0) {
