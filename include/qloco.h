@@ -93,7 +93,10 @@ typedef struct qloco_srbd_spec {
                              /*    equality rows, rho_eq = 1e3 rho), Ruiz over the  */
                              /*    full P and A (ConvexMpc.cpp:162-264,             */
                              /*    A1RobotControl.cpp:557-578); DESIGN.md §3e       */
-  int32_t reserved[5];
+  int32_t reserved[5];       /* zero, but for the debug bit reserved[0] & 1: the one-  */
+                             /* wave literal kernel builds its G^-1 horizon tables  */
+                             /* per instance although the spec has host tables       */
+                             /* (qloco_srbd_lit_tables); both paths stay tested      */
 } qloco_srbd_spec;
 
 /* Per-instance record of the persistent solver (spec.warm_start == 2),
@@ -116,6 +119,20 @@ typedef struct qloco_srbd_spec {
 
 /* Go1 SRBD constants + OSQP default settings. */
 void qloco_srbd_spec_default(qloco_srbd_spec *spec);
+
+/* Host-side G^-1 horizon tables of the literal QP's wrench-space kernels
+ * (DESIGN.md §3l): a function of (horizon, dt, q_weights) alone where
+ * q_weights[6] == q_weights[7] (isotropic omega x / y weights), computed once
+ * per spec and passed to the one-wave kernel (horizon <= 10) with its
+ * arguments.  gtab[gtab_len >= NT * NT * 6], NT = 10 for horizon <= 10 and 20
+ * up to 20: (row step, column step, axis) in the kernels' column-space order
+ * (two waves: step r >= H = ceil(N / 2) at 10 + r - H), float32 of the
+ * float64 inverses of alpha_a K0 + beta_a K2, zero on padding steps.
+ * *s_scale = 1 / sqrt(2 q_weights[6]), *gmx = max diag G^-1.  *served = 0 and
+ * nothing else written where the kernels build the tables per instance
+ * (anisotropic omega weights).  Host pointers; no device work. */
+int qloco_srbd_lit_tables(const qloco_srbd_spec *spec, float *gtab, int64_t gtab_len,
+                          float *s_scale, float *gmx, int32_t *served);
 
 /* Largest stance-variable count the compiled kernels accept (3 x 4 x 20). */
 int qloco_srbd_max_stance_vars(void);

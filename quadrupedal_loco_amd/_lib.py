@@ -76,6 +76,7 @@ SIGNATURES = {
     "qloco_srbd_spec_default": (None, [C.POINTER(SrbdSpec)]),
     "qloco_srbd_max_stance_vars": (C.c_int, []),
     "qloco_srbd_route": (C.c_int, [C.POINTER(SrbdSpec)]),
+    "qloco_srbd_lit_tables": (C.c_int, [C.POINTER(SrbdSpec), vp, i64, vp, vp, vp]),
     "qloco_srbd_solve": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                    vp, vp, vp]),
     "qloco_srbd_solve_ex": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,

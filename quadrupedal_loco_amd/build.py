@@ -34,6 +34,7 @@ SOURCES = [
     "qloco_a1est.hip",
     "qloco_mgpu.hip",
     "qloco_gen.cpp",
+    "qloco_srbd_tables.cpp",
 ]
 # per-file extra flags: the fp64 active-set kernel keeps the restatement's
 # exact operation sequence (no FMA contraction)
@@ -71,7 +72,7 @@ def build(verbose=False, jobs=8):
         if src.endswith(".hip"):
             cmd = ([HIPCC, "--offload-arch=" + ARCH, "-x", "hip"] + COMMON + EXTRA.get(src, []) +
                    ["-c", path, "-o", obj])
-        else:  # host-only C++ (generator): exact IEEE, no contraction
+        else:  # host-only C++ (generator, literal G^-1 tables): exact IEEE, no contraction
             cmd = [HIPCC, "-x", "c++"] + COMMON + ["-ffp-contract=off", "-c", path, "-o", obj]
         cmds.append(cmd)
     procs = []

@@ -47,6 +47,7 @@
 
 #include "qloco_common.hpp"
 #include "qloco_srbd_core.hpp"
+#include "qloco_srbd_tables.hpp"
 
 // The KKT inverse is the register-row DPP Gauss-Jordan below.  The
 // matrix-core block Gauss-Jordan forms measured against it (as accurate once
@@ -1647,6 +1648,10 @@ extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, c
   if (srbd_route_of(a) <= QLOCO_ROUTE_LIT_TWO_WAVE) {
     // the literal QP at N <= 20 through the wrench space: one wave per
     // instance for N <= 10, two for 11..20 (qloco_srbd_lit.hip)
+    // one wave: the spec's G^-1 horizon tables from the host cache, in the
+    // kernel arguments; reserved[0] & 1 keeps the in-kernel path
+    if (a.N <= kLitN && !(spec->reserved[0] & 1))
+      a.lit_tables = srbd_lit_tables_cached(a.N, a.dt, a.q2, a.lit_gtab, &a.lit_sq, &a.lit_gmx) ? 1 : 0;
     const int rc = srbd_lit_launch(a, ws, st);
     if (rc != QLOCO_OK) return rc;
   } else if (top == 0 || a.literal) {

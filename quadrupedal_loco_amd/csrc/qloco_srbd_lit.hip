@@ -372,8 +372,21 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
 
   // ---------------- 2. SRBD model (ConvexMpc.cpp:111-160, compute_grf :502-549)
   const float yaw = S.x0[2];
-  const float cy = cosf(yaw), sy = sinf(yaw);
+  float sy, cy;
+  sincosf(yaw, &sy, &cy);  // one range reduction; the bits of sinf / cosf
   const float R00 = cy, R01 = sy, R10 = -sy, R11 = cy;  // A1RobotControl.cpp:506-508
+  if constexpr (W == 1) {
+    // host G^-1 tables (isotropic omega weights): the omega
+    // x / y pair's S = Q^-1/2 V with V = Rz' -- the eigenvectors of
+    // Rz' diag(q_theta) Rz / q_omega for every yaw -- from the model's cos / sin
+    if (a.lit_tables && tid == 0) {
+      const float sq = a.lit_sq;
+      S.sc[0].sxy[0][0] = sq * cy;
+      S.sc[0].sxy[0][1] = -(sq * sy);
+      S.sc[0].sxy[1][0] = sq * sy;
+      S.sc[0].sxy[1][1] = sq * cy;
+    }
+  }
   float Ii[3][3];
   {
     const float *I = a.inertia;
@@ -566,33 +579,37 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
       const f2v be = S.beps[wl][wl];
       pdiag[h] = valid[h] ? fmaf(kk.y, be.y, kk.x * be.x) + r2v[h] : 0.0f;
     }
-    // this lane's (beta, eps) rows, per slot (registers for the whole of
-    // Ruiz: every column step reuses them)
-    float bet[2][12], eps[2][12];
+    // this lane's (beta, eps) row as pairs of adjacent columns (w, w + 1),
+    // registers for the whole of Ruiz.  Both slots of a lane sit on the same
+    // wrench column (60 % 12 == 0), so one row serves both: 24 registers, and
+    // the pairs {beta_w, beta_w+1}, {eps_w, eps_w+1} and {D_w, D_w+1} (as
+    // read) are the packed operands as they stand -- no pair-building moves
+    // (DESIGN.md §3l).  A slot that holds no variable computes on the lane's
+    // row all the same and is masked at the end.
+    f2v be2[6], ep2[6];
+    {
+      const int wl = lane < 60 ? lane % 12 : 0;
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int wl = h == 0 ? (valid[0] ? lane % 12 : 0) : (valid[1] ? (60 + lane) % 12 : 0);
-#pragma unroll
-      for (int w = 0; w < 12; ++w) {
-        const f2v be = S.beps[wl][w];
-        bet[h][w] = valid[h] ? be.x : 0.0f;
-        eps[h][w] = valid[h] ? be.y : 0.0f;
+      for (int p = 0; p < 6; ++p) {
+        const f4v q = *reinterpret_cast<const f4v *>(&S.beps[wl][2 * p]);  // (beta, eps) of w, w + 1
+        be2[p] = (f2v){q.x, q.z};
+        ep2[p] = (f2v){q.y, q.w};
       }
     }
     // row inf-norms |P_vc| D_c of both slots' rows in one sweep over the 12N
     // columns, step-major: per column step the K0 / K2 weights of the two
     // rows' steps and the step's 12 column scales (same-address LDS reads,
-    // a broadcast), then 12 entries per row from the (beta, eps) rows
+    // a broadcast), then 12 entries per row from the (beta, eps) row: every
+    // entry fma(K2, eps, K0 beta) D, whatever the packing
     auto row_norms = [&](bool scaled, float (&m)[2]) {
       // loop-invariant tables: opaque per call (no hoisting of all 240 entries)
 #pragma unroll
-      for (int h = 0; h < 2; ++h)
-#pragma unroll
-        for (int w = 0; w < 12; ++w) asm volatile("" : "+v"(bet[h][w]), "+v"(eps[h][w]));
-      // both slots' rows as fp32 pairs (v_pk_fma / v_pk_mul), two max chains
-      // each; the next column step's LDS reads are issued before this step's
-      // arithmetic (one step of look-ahead, no more: all ten would be live)
-      f2v ma = (f2v)(0.0f), mb = (f2v)(0.0f);
+      for (int p = 0; p < 6; ++p) asm volatile("" : "+v"(be2[p]), "+v"(ep2[p]));
+      // column pairs as fp32 pairs (v_pk_fma / v_pk_mul, K0 / K2 broadcast
+      // from the pair as loaded), two max chains per slot; the next column
+      // step's LDS reads are issued before this step's arithmetic (one step
+      // of look-ahead, no more: all ten would be live)
+      float ma[2] = {0.0f, 0.0f}, mb[2] = {0.0f, 0.0f};
       const f4v one4 = (f4v)(1.0f);
       f2v k0 = S.k0k2[cst[0]][0], k1 = S.k0k2[cst[1]][0];
       f4v da = scaled ? reinterpret_cast<const f4v *>(&S.dcol[0])[0] : one4,
@@ -606,19 +623,35 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         const f4v *dcn = reinterpret_cast<const f4v *>(&S.dcol[12 * kn]);
         const f4v dan = scaled ? dcn[0] : one4, dbn = scaled ? dcn[1] : one4, ddn = scaled ? dcn[2] : one4;
         __builtin_amdgcn_sched_barrier(0);
-        const f2v kx = {k0.x, k1.x}, ky = {k0.y, k1.y};
-        const float dv[12] = {da.x, da.y, da.z, da.w, db.x, db.y, db.z, db.w, dd.x, dd.y, dd.z, dd.w};
+        const f2v dv[6] = {{da.x, da.y}, {da.z, da.w}, {db.x, db.y}, {db.z, db.w}, {dd.x, dd.y}, {dd.z, dd.w}};
+        // four independent chains at a time (slot c >> 1, column pair
+        // 2 g + (c & 1)), stage by stage: a packed op's result is read three
+        // instructions later, so no hazard padding between dependent ops
 #pragma unroll
-        for (int w = 0; w < 12; ++w) {
-          const f2v be = {bet[0][w], bet[1][w]}, ep = {eps[0][w], eps[1][w]};
-          const f2v p = __builtin_elementwise_fma(ky, ep, kx * be) * (f2v)(dv[w]);
-          f2v &acc = (w & 1) ? mb : ma;
-          acc.x = fmaxf(acc.x, fabsf(p.x));
-          acc.y = fmaxf(acc.y, fabsf(p.y));
+        for (int g = 0; g < 3; ++g) {
+          f2v t[4];
+#pragma unroll
+          for (int c = 0; c < 4; ++c) t[c] = (f2v)((c >> 1) ? k1.x : k0.x) * be2[2 * g + (c & 1)];
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int c = 0; c < 4; ++c)
+            t[c] = __builtin_elementwise_fma((f2v)((c >> 1) ? k1.y : k0.y), ep2[2 * g + (c & 1)], t[c]);
+          __builtin_amdgcn_sched_barrier(0);
+          if (scaled) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) t[c] = t[c] * dv[2 * g + (c & 1)];
+            __builtin_amdgcn_sched_barrier(0);
+          }
+#pragma unroll
+          for (int c = 0; c < 4; ++c) {
+            float &acc = (c & 1) ? mb[c >> 1] : ma[c >> 1];
+            acc = fmaxf(fmaxf(acc, fabsf(t[c].x)), fabsf(t[c].y));
+          }
+          __builtin_amdgcn_sched_barrier(0);
         }
         // pin the step's arithmetic here (no sinking into a late masked block
         // that would keep every step's loads live)
-        asm volatile("" : "+v"(ma), "+v"(mb));
+        asm volatile("" : "+v"(ma[0]), "+v"(ma[1]), "+v"(mb[0]), "+v"(mb[1]));
         __builtin_amdgcn_sched_barrier(0);
         k0 = k0n;
         k1 = k1n;
@@ -626,8 +659,8 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         db = dbn;
         dd = ddn;
       }
-      m[0] = valid[0] ? fmaxf(ma.x, mb.x) : 0.0f;
-      m[1] = valid[1] ? fmaxf(ma.y, mb.y) : 0.0f;
+      m[0] = valid[0] ? fmaxf(ma[0], mb[0]) : 0.0f;
+      m[1] = valid[1] ? fmaxf(ma[1], mb[1]) : 0.0f;
     };
     float cnP[2];
     {
@@ -917,8 +950,37 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
   // isaac_a1_mpc.yaml); with q_omega_x = q_omega_y S is Rz' / sqrt(q_omega).
   // One N x N Gauss-Jordan per (axis, row) lane in float64, once per solve,
   // instead of a 6N x 6N one per factorisation.
-  float gmx;  // max diag G^-1 (block-uniform; an SPD matrix's largest entry)
-  {
+  //
+  // Isotropic omega weights (q_omega_x = q_omega_y: Go1's default set, the
+  // reference's gazebo and hardware sets): lambda = (q_theta_x, q_theta_y) /
+  // q_omega for every yaw, so all six blocks depend on the spec alone and
+  // come from the host with the kernel arguments (one wave: 600 floats;
+  // qloco_srbd_tables.cpp); S was stored with the model.
+  float gmx = 0.0f;  // max diag G^-1 (block-uniform; an SPD matrix's largest entry)
+  bool host_tables = false;  // wave-uniform
+  if constexpr (W == 1) host_tables = a.lit_tables != 0;
+  if (host_tables) {
+    if constexpr (W == 1) {
+      static_assert(sizeof(S.gtab) == sizeof(a.lit_gtab) && offsetof(LitLds<1>, gtab) % 16 == 0 &&
+                        offsetof(SrbdArgs, lit_gtab) % 16 == 0,
+                    "the host tables are copied as f4v into gtab");
+      constexpr int NV = (int)(sizeof(a.lit_gtab) / (sizeof(float) * 4));
+      const int fl = fresh_lane();
+      // read through the kernarg segment itself (SrbdArgs is the kernel's one
+      // parameter): a lane-indexed read of the by-value copy would put the
+      // whole argument block into scratch
+      typedef const f4v __attribute__((address_space(4))) *KernargF4;
+      typedef const char __attribute__((address_space(4))) *KernargBytes;
+      const KernargBytes args = (KernargBytes)__builtin_amdgcn_kernarg_segment_ptr();
+      const KernargF4 src = (KernargF4)(args + offsetof(SrbdArgs, lit_gtab));
+      f4v *dst = reinterpret_cast<f4v *>(&S.gtab[0][0][0]);
+#pragma unroll
+      for (int i = 0; i < (NV + 63) / 64; ++i)
+        if (64 * i + fl < NV) dst[64 * i + fl] = src[64 * i + fl];
+      gmx = sgpr_f(a.lit_gmx);
+      bsync<W>();
+    }
+  } else {
     double row[NS];
     const int r = tid;
     const bool live = r < 6 * N;
