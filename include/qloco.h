@@ -640,6 +640,104 @@ int qloco_a1_ekf_get_state(int64_t batch, const void *workspace, double *x, doub
 int qloco_a1_ekf_set_state(int64_t batch, void *workspace, const double *x, const double *P,
                            void *stream);
 
+/* ====================================================================== */
+/* 13. A1 gait plan, swing-leg control, terrain pitch and joint torques,   */
+/*    batched (fp64)                                                       */
+/*    replaces A1RobotControl::update_plan + generate_swing_legs_ctrl      */
+/*    (unitree_ros/a1_cpp_open_source/src/A1RobotControl.cpp:149-292, as    */
+/*    GazeboA1ROS.cpp:199-202 calls them back to back), the                */
+/*    stance_leg_control_type == 1 preamble of compute_grf (:341-380, with  */
+/*    compute_walking_surface :604-620 and Utils.cpp:44-62) and             */
+/*    compute_joint_torques (:294-324).  With sections 9 / 1, 11 and 12 one */
+/*    A1 control tick runs on the device: leg kinematics, plan + swing,     */
+/*    EKF, terrain pitch, QP or MPC, joint torques.                         */
+/* ====================================================================== */
+/* Defaults from A1CtrlStates::reset() (A1CtrlStates.h:20-132), A1Params.h:38-45
+ * and the A1RobotControl constructor (:53-58).  a1_ctrl.launch's yaml
+ * overrides several of them through resetFromROSParam (A1CtrlStates.h:134-317:
+ * the gait counter speeds, default_foot_pos, kp_foot / kd_foot / km_foot among
+ * others); a caller that runs with that yaml passes its values here.  3x4
+ * matrices are column-major, legs FL, FR, RL, RR. */
+typedef struct qloco_a1_ctrl_params {
+  double counter_per_gait, counter_per_swing; /* 240, 120 */
+  double gait_counter_speed[4];               /* 2 */
+  double gait_counter_reset[4];               /* gait_counter_reset(): 0, 120, 120, 0 */
+  double default_foot_pos[12];
+  double control_dt;                          /* 0.0025 */
+  double kp_foot[12], kd_foot[12], km_foot[3], torques_gravity[12];
+  double foot_delta_x_limit, foot_delta_y_limit; /* 0.1, 0.1 */
+  double foot_force_low;                         /* FOOT_FORCE_LOW 30 */
+  double foot_swing_clearance1, foot_swing_clearance2; /* (double)0.0f, (double)0.4f */
+  int32_t recent_contact_window; /* 60, at most QLOCO_A1_CTRL_RC_WINDOW_MAX  */
+  int32_t terrain_window;        /* 100, at most QLOCO_A1_CTRL_TER_WINDOW_MAX */
+  int32_t torque_holdoff_ticks;  /* 10: torques are zero while mpc_init_counter < 10 */
+  int32_t reserved[5];
+} qloco_a1_ctrl_params;
+void qloco_a1_ctrl_params_default(qloco_a1_ctrl_params *p);
+/* The member state of every robot lives in a device workspace of
+ * qloco_a1_ctrl_workspace_bytes(batch) bytes (-1 for batch <= 0), field-major
+ * with slot-major filter rings.  get_state / set_state move it out of / into
+ * a dense array of QLOCO_A1_CTRL_STATE doubles per robot (flags and counts as
+ * 0.0 / 1.0 / integers in doubles):
+ *   [0:4] gait_counter | [4:8] plan_contacts | [8:12] early_contacts |
+ *   [12:16] contacts | [16:28] foot_pos_start | [28:40] foot_pos_rel_last_time |
+ *   [40:52] foot_pos_target_last_time | [52:64] foot_pos_target_rel |
+ *   [64:76] foot_pos_recent_contact | [76:88] foot_forces_kin |
+ *   [88:100] joint_torques (the value the NaN guard holds) |
+ *   [100] mpc_init_counter | [101] terrain_pitch_angle |
+ *   recent-contact filters: [102:106] fill count per leg | [106:110] index of
+ *   the oldest slot per leg | [110:122] sum_ | [122:134] correction_ (3x4) |
+ *   terrain filter: [134] fill | [135] oldest slot | [136] sum_ | [137] correction_ |
+ *   [138:858] recent-contact ring, 60 slots x 12 | [858:958] terrain ring.
+ * The x, y and z filters of a leg always advance together and share fill
+ * count and head.  The deque of MovingWindowFilter is slots head, head + 1,
+ * ... (mod window), fill of them. */
+#define QLOCO_A1_CTRL_STATE 958
+#define QLOCO_A1_CTRL_RC_WINDOW_MAX 60
+#define QLOCO_A1_CTRL_TER_WINDOW_MAX 100
+int64_t qloco_a1_ctrl_workspace_bytes(int64_t batch);
+/* The A1CtrlStates::reset() / constructor values: everything zero, the gait
+ * counters at gait_counter_reset, empty filters. */
+int qloco_a1_ctrl_reset(const qloco_a1_ctrl_params *prm, int64_t batch, void *workspace,
+                        void *stream);
+/* update_plan then generate_swing_legs_ctrl, one tick of every robot.  Device
+ * pointers: dt[B], movement_mode[B] (int32; 0 standstill), root_pos[B*3],
+ * root_lin_vel[B*3], root_lin_vel_d[B*3], root_rot_mat[B*9], root_rot_mat_z
+ * [B*9] (3x3 col-major), foot_pos_abs[B*12] (3x4 col-major), foot_force[B*4].
+ * Outputs: contacts[B*4] (uint8) required -- the `contacts` input of sections
+ * 9 and 1; optional (NULL): plan_contacts / early_contacts [B*4] (uint8),
+ * gait_counter[B*4], foot_pos_target_rel / _abs / _world [B*12],
+ * foot_pos_cur[B*12], foot_forces_kin[B*12], foot_pos_recent_contact[B*12]. */
+int qloco_a1_ctrl_plan_swing(const qloco_a1_ctrl_params *prm, int64_t batch, void *workspace,
+                             const double *dt, const int32_t *movement_mode,
+                             const double *root_pos, const double *root_lin_vel,
+                             const double *root_lin_vel_d, const double *root_rot_mat,
+                             const double *root_rot_mat_z, const double *foot_pos_abs,
+                             const double *foot_force, uint8_t *contacts, uint8_t *plan_contacts,
+                             uint8_t *early_contacts, double *gait_counter,
+                             double *foot_pos_target_rel, double *foot_pos_target_abs,
+                             double *foot_pos_target_world, double *foot_pos_cur,
+                             double *foot_forces_kin, double *foot_pos_recent_contact,
+                             void *stream);
+/* Terrain pitch: fits the plane through the workspace's
+ * foot_pos_recent_contact, filters its angle against the ground plane (only
+ * while root_pos[2] > 0.1), clamps to +-0.5 and writes root_euler_d[B*3]
+ * entry 1 (in/out; the other entries are not touched).  Outputs:
+ * terrain_pitch_angle[B]; surf_coef[B*3] optional. */
+int qloco_a1_ctrl_terrain(const qloco_a1_ctrl_params *prm, int64_t batch, void *workspace,
+                          const double *root_pos, double *root_euler_d,
+                          double *terrain_pitch_angle, double *surf_coef, void *stream);
+/* compute_joint_torques: j_foot[B*36] as section 11 writes it,
+ * foot_forces_grf[B*12] as sections 1 and 9 write it (body frame, 3x4
+ * col-major); reads contacts and foot_forces_kin from the workspace.
+ * Output: joint_torques[B*12]. */
+int qloco_a1_ctrl_joint_torques(const qloco_a1_ctrl_params *prm, int64_t batch, void *workspace,
+                                const double *j_foot, const double *foot_forces_grf,
+                                double *joint_torques, void *stream);
+/* Dense state[B * QLOCO_A1_CTRL_STATE] out of / into the workspace. */
+int qloco_a1_ctrl_get_state(int64_t batch, const void *workspace, double *state, void *stream);
+int qloco_a1_ctrl_set_state(int64_t batch, void *workspace, const double *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

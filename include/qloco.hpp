@@ -18,6 +18,10 @@
  *                                    (PRMPCClass.h:69-71; gait_fast.cpp:620)
  *   ConvexMpcBatch                <- A1RobotControl::compute_grf MPC branch +
  *                                    ConvexMpc (A1RobotControl.cpp:452-600)
+ *   A1RobotControlBatch           <- A1RobotControl::update_plan / generate_swing_legs_ctrl /
+ *                                    compute_joint_torques (a1_cpp_open_source/src/
+ *                                    A1RobotControl.cpp:149-324) and the terrain-pitch
+ *                                    preamble of compute_grf (:341-380)
  *   A1BasicEKFBatch               <- A1BasicEKF (a1_cpp_open_source/src/A1BasicEKF.h:25-72;
  *                                    GazeboA1ROS.cpp:204-209)
  *   Kinematicclass                <- go1_rt_control Kinematicclass
@@ -323,6 +327,59 @@ class A1BasicEKFBatch {
   int32_t *d_mode_;
   uint8_t *d_ct_;
   void stage(const A1EstState *states, double dt);
+};
+
+// ------------------------------------------------------------------------
+// A1RobotControl's update_plan, generate_swing_legs_ctrl, terrain-pitch
+// preamble of compute_grf and compute_joint_torques (A1RobotControl.cpp:149-380)
+// over B robots.  A1CtrlState carries the A1CtrlStates fields those functions
+// read and write, under their names; the members that persist from tick to
+// tick (gait counters, *_last_time, the moving-window filters, ...) stay on the
+// device (qloco_a1_ctrl_*) and are mirrored into the host fields after every
+// call.  The reference calls update_plan and generate_swing_legs_ctrl back to
+// back (GazeboA1ROS.cpp:199-202): update_plan only stages its inputs, the
+// device call runs in generate_swing_legs_ctrl, which then fills the outputs
+// of both (plan_contacts, gait_counter and the foot_pos_target_* arrays
+// included).  Calling generate_swing_legs_ctrl without update_plan throws.
+struct A1CtrlState {
+  int movement_mode;
+  double root_pos[3], root_lin_vel[3], root_lin_vel_d[3], root_euler_d[3];
+  double root_rot_mat[9], root_rot_mat_z[9];  // 3x3 col-major
+  double foot_pos_abs[12];                    // 3x4 col-major, legs FL, FR, RL, RR
+  double foot_force[4];
+  double j_foot[36];            // the four 3x3 diagonal blocks, each col-major
+  double foot_forces_grf[12];
+  // written
+  double gait_counter[4];
+  bool plan_contacts[4], early_contacts[4], contacts[4];
+  double foot_pos_target_rel[12], foot_pos_target_abs[12], foot_pos_target_world[12];
+  double foot_pos_cur[12], foot_forces_kin[12], foot_pos_recent_contact[12];
+  double terrain_pitch_angle;
+  double joint_torques[12];
+};
+
+class A1RobotControlBatch {
+ public:
+  A1RobotControlBatch(int batch, const qloco_a1_ctrl_params *params = nullptr);
+  void update_plan(A1CtrlState *states, double dt);               // stages only
+  void generate_swing_legs_ctrl(A1CtrlState *states, double dt);  // plan + swing on the device
+  void compute_terrain_pitch(A1CtrlState *states);  // writes root_euler_d[1], terrain_pitch_angle
+  void compute_joint_torques(A1CtrlState *states);
+  // dense member state, B * QLOCO_A1_CTRL_STATE doubles (include/qloco.h section 13)
+  void get_state(double *state);
+  void reset();
+  qloco_a1_ctrl_params params;
+  int batch() const { return batch_; }
+
+ private:
+  int batch_;
+  bool staged_ = false;
+  double staged_dt_ = 0.0;
+  DeviceArena arena_;
+  void *d_ws_;
+  double *d_in_, *d_out_, *d_rec_;
+  int32_t *d_mode_;
+  uint8_t *d_ct_;
 };
 
 // ------------------------------------------------------------------------

@@ -64,6 +64,20 @@ class A1EkfParams(C.Structure):
                 ("assume_flat_ground", C.c_int32), ("reserved", C.c_int32 * 7)]
 
 
+class A1CtrlParams(C.Structure):
+    """Mirror of `qloco_a1_ctrl_params`."""
+    _fields_ = [("counter_per_gait", C.c_double), ("counter_per_swing", C.c_double),
+                ("gait_counter_speed", C.c_double * 4), ("gait_counter_reset", C.c_double * 4),
+                ("default_foot_pos", C.c_double * 12), ("control_dt", C.c_double),
+                ("kp_foot", C.c_double * 12), ("kd_foot", C.c_double * 12),
+                ("km_foot", C.c_double * 3), ("torques_gravity", C.c_double * 12),
+                ("foot_delta_x_limit", C.c_double), ("foot_delta_y_limit", C.c_double),
+                ("foot_force_low", C.c_double), ("foot_swing_clearance1", C.c_double),
+                ("foot_swing_clearance2", C.c_double), ("recent_contact_window", C.c_int32),
+                ("terrain_window", C.c_int32), ("torque_holdoff_ticks", C.c_int32),
+                ("reserved", C.c_int32 * 5)]
+
+
 vp = C.c_void_p
 i64 = C.c_int64
 i32 = C.c_int32
@@ -123,6 +137,14 @@ SIGNATURES = {
     "qloco_a1_ekf_update": (C.c_int, [C.POINTER(A1EkfParams), i64] + [vp] * 13),
     "qloco_a1_ekf_get_state": (C.c_int, [i64, vp, vp, vp, vp]),
     "qloco_a1_ekf_set_state": (C.c_int, [i64, vp, vp, vp, vp]),
+    "qloco_a1_ctrl_params_default": (None, [C.POINTER(A1CtrlParams)]),
+    "qloco_a1_ctrl_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_a1_ctrl_reset": (C.c_int, [C.POINTER(A1CtrlParams), i64, vp, vp]),
+    "qloco_a1_ctrl_plan_swing": (C.c_int, [C.POINTER(A1CtrlParams), i64] + [vp] * 21),
+    "qloco_a1_ctrl_terrain": (C.c_int, [C.POINTER(A1CtrlParams), i64] + [vp] * 6),
+    "qloco_a1_ctrl_joint_torques": (C.c_int, [C.POINTER(A1CtrlParams), i64] + [vp] * 5),
+    "qloco_a1_ctrl_get_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_a1_ctrl_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),
     "qloco_mgpu_gather_rows": (C.c_int, [i64, i32, i32, vp]),
     "qloco_mgpu_reorder": (C.c_int, [i64, i32, i32, i32, vp, vp, vp, vp, vp]),

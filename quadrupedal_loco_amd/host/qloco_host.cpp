@@ -705,6 +705,152 @@ void A1BasicEKFBatch::get_state(double *x, double *P) {
 }
 
 
+// ---------------------------------------------------------------- A1RobotControlBatch
+// device staging, doubles per robot, field-major: dt 1 | root_pos 3 |
+// root_lin_vel 3 | root_lin_vel_d 3 | root_rot_mat 9 | root_rot_mat_z 9 |
+// foot_pos_abs 12 | foot_force 4 | root_euler_d 3 | j_foot 36 | grf 12 (= 95);
+// outputs gait_counter 4 | target rel / abs / world, cur, fkin, recent 6 x 12 |
+// angle 1 | torques 12 (= 89); flags contacts / plan / early 3 x 4 bytes
+namespace {
+constexpr size_t kCI_DT = 0, kCI_POS = 1, kCI_VEL = 4, kCI_VELD = 7, kCI_ROT = 10, kCI_ROTZ = 19,
+                 kCI_FEET = 28, kCI_FORCE = 40, kCI_EUL = 44, kCI_J = 47, kCI_GRF = 83, kCI_N = 95;
+constexpr size_t kCO_GC = 0, kCO_T = 4, kCO_ANG = 76, kCO_TAU = 77, kCO_N = 89;
+}  // namespace
+
+A1RobotControlBatch::A1RobotControlBatch(int batch, const qloco_a1_ctrl_params *p)
+    : batch_(positive_batch(batch, "A1RobotControlBatch")) {
+  if (p) params = *p;
+  else qloco_a1_ctrl_params_default(&params);
+  const size_t B = batch;
+  const int64_t ws = qloco_a1_ctrl_workspace_bytes(batch);
+  if (ws < 0) throw Error("qloco_a1_ctrl_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_in_ = dalloc<double>(arena_, B * kCI_N);
+  d_out_ = dalloc<double>(arena_, B * kCO_N);
+  d_rec_ = dalloc<double>(arena_, B * QLOCO_A1_CTRL_STATE);
+  d_mode_ = dalloc<int32_t>(arena_, B);
+  d_ct_ = dalloc<uint8_t>(arena_, B * 12);
+  reset();
+}
+
+void A1RobotControlBatch::reset() {
+  abi_ok(qloco_a1_ctrl_reset(&params, batch_, d_ws_, arena_.stream()), "qloco_a1_ctrl_reset");
+  arena_.sync();
+  staged_ = false;
+}
+
+void A1RobotControlBatch::update_plan(A1CtrlState *s, double dt) {
+  if (!s) throw Error("A1RobotControlBatch::update_plan: null states", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  std::vector<double> in(B * kCI_FORCE + 4 * B);
+  std::vector<int32_t> mode(B);
+  for (size_t b = 0; b < B; ++b) {
+    in[kCI_DT * B + b] = dt;
+    mode[b] = s[b].movement_mode;
+    for (int k = 0; k < 3; ++k) {
+      in[kCI_POS * B + 3 * b + k] = s[b].root_pos[k];
+      in[kCI_VEL * B + 3 * b + k] = s[b].root_lin_vel[k];
+      in[kCI_VELD * B + 3 * b + k] = s[b].root_lin_vel_d[k];
+    }
+    for (int k = 0; k < 9; ++k) {
+      in[kCI_ROT * B + 9 * b + k] = s[b].root_rot_mat[k];
+      in[kCI_ROTZ * B + 9 * b + k] = s[b].root_rot_mat_z[k];
+    }
+    for (int k = 0; k < 12; ++k) in[kCI_FEET * B + 12 * b + k] = s[b].foot_pos_abs[k];
+    for (int k = 0; k < 4; ++k) in[kCI_FORCE * B + 4 * b + k] = s[b].foot_force[k];
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  arena_.upload(d_mode_, mode.data(), sizeof(int32_t) * B);
+  arena_.sync();  // the host vectors go out of scope
+  staged_ = true;
+  staged_dt_ = dt;
+}
+
+void A1RobotControlBatch::generate_swing_legs_ctrl(A1CtrlState *s, double dt) {
+  if (!s) throw Error("A1RobotControlBatch::generate_swing_legs_ctrl: null states", QLOCO_ERR_ARG);
+  if (!staged_ || dt != staged_dt_)
+    throw Error("A1RobotControlBatch::generate_swing_legs_ctrl: update_plan(states, dt) first",
+                QLOCO_ERR_ARG);
+  staged_ = false;
+  const size_t B = batch_;
+  double *in = d_in_, *o = d_out_, *t = o + kCO_T * B;
+  abi_ok(qloco_a1_ctrl_plan_swing(&params, batch_, d_ws_, in, d_mode_, in + kCI_POS * B,
+                                  in + kCI_VEL * B, in + kCI_VELD * B, in + kCI_ROT * B,
+                                  in + kCI_ROTZ * B, in + kCI_FEET * B, in + kCI_FORCE * B, d_ct_,
+                                  d_ct_ + 4 * B, d_ct_ + 8 * B, o, t, t + 12 * B, t + 24 * B,
+                                  t + 36 * B, t + 48 * B, t + 60 * B, arena_.stream()),
+         "qloco_a1_ctrl_plan_swing");
+  std::vector<double> out(B * kCO_ANG);
+  std::vector<uint8_t> ct(B * 12);
+  arena_.download(out.data(), d_out_, sizeof(double) * out.size());
+  arena_.download(ct.data(), d_ct_, ct.size());
+  arena_.sync();
+  for (size_t b = 0; b < B; ++b) {
+    for (int l = 0; l < 4; ++l) {
+      s[b].gait_counter[l] = out[4 * b + l];
+      s[b].contacts[l] = ct[4 * b + l] != 0;
+      s[b].plan_contacts[l] = ct[4 * B + 4 * b + l] != 0;
+      s[b].early_contacts[l] = ct[8 * B + 4 * b + l] != 0;
+    }
+    double *dst[6] = {s[b].foot_pos_target_rel, s[b].foot_pos_target_abs, s[b].foot_pos_target_world,
+                      s[b].foot_pos_cur,        s[b].foot_forces_kin,     s[b].foot_pos_recent_contact};
+    for (int f = 0; f < 6; ++f)
+      for (int k = 0; k < 12; ++k) dst[f][k] = out[(kCO_T + 12 * f) * B + 12 * b + k];
+    for (int k = 0; k < 12; ++k) s[b].joint_torques[k] = 0.0;  // :210
+  }
+}
+
+void A1RobotControlBatch::compute_terrain_pitch(A1CtrlState *s) {
+  if (!s) throw Error("A1RobotControlBatch::compute_terrain_pitch: null states", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  std::vector<double> in(6 * B);
+  for (size_t b = 0; b < B; ++b)
+    for (int k = 0; k < 3; ++k) {
+      in[3 * b + k] = s[b].root_pos[k];
+      in[3 * B + 3 * b + k] = s[b].root_euler_d[k];
+    }
+  double *pos = d_in_ + kCI_POS * B, *eul = d_in_ + kCI_EUL * B, *ang = d_out_ + kCO_ANG * B;
+  arena_.upload(pos, in.data(), sizeof(double) * 3 * B);
+  arena_.upload(eul, in.data() + 3 * B, sizeof(double) * 3 * B);
+  abi_ok(qloco_a1_ctrl_terrain(&params, batch_, d_ws_, pos, eul, ang, nullptr, arena_.stream()),
+         "qloco_a1_ctrl_terrain");
+  std::vector<double> out(4 * B);
+  arena_.download(out.data(), eul, sizeof(double) * 3 * B);
+  arena_.download(out.data() + 3 * B, ang, sizeof(double) * B);
+  arena_.sync();
+  for (size_t b = 0; b < B; ++b) {
+    s[b].root_euler_d[1] = out[3 * b + 1];
+    s[b].terrain_pitch_angle = out[3 * B + b];
+  }
+}
+
+void A1RobotControlBatch::compute_joint_torques(A1CtrlState *s) {
+  if (!s) throw Error("A1RobotControlBatch::compute_joint_torques: null states", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  std::vector<double> in(48 * B);
+  for (size_t b = 0; b < B; ++b) {
+    for (int k = 0; k < 36; ++k) in[36 * b + k] = s[b].j_foot[k];
+    for (int k = 0; k < 12; ++k) in[36 * B + 12 * b + k] = s[b].foot_forces_grf[k];
+  }
+  double *J = d_in_ + kCI_J * B, *grf = d_in_ + kCI_GRF * B, *tau = d_out_ + kCO_TAU * B;
+  arena_.upload(J, in.data(), sizeof(double) * 48 * B);  // j_foot and grf are adjacent
+  abi_ok(qloco_a1_ctrl_joint_torques(&params, batch_, d_ws_, J, grf, tau, arena_.stream()),
+         "qloco_a1_ctrl_joint_torques");
+  std::vector<double> out(12 * B);
+  arena_.download(out.data(), tau, sizeof(double) * 12 * B);
+  arena_.sync();
+  for (size_t b = 0; b < B; ++b)
+    for (int k = 0; k < 12; ++k) s[b].joint_torques[k] = out[12 * b + k];
+}
+
+void A1RobotControlBatch::get_state(double *state) {
+  if (!state) throw Error("A1RobotControlBatch::get_state: null output", QLOCO_ERR_ARG);
+  abi_ok(qloco_a1_ctrl_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_a1_ctrl_get_state");
+  arena_.download(state, d_rec_, sizeof(double) * (size_t)batch_ * QLOCO_A1_CTRL_STATE);
+  arena_.sync();
+}
+
+
 // ------------------------------------------------------------------------
 // Kinematicclass -> qloco_leg_fk / qloco_leg_ik
 Kinematicclass::Kinematicclass(int max_legs) : cap_(0) {
