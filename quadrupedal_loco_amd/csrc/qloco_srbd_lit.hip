@@ -215,20 +215,25 @@ __device__ __forceinline__ void lit_invert(LitLds<1> &S, int lane, int ncol, Row
     constexpr int k = decltype(kc)::value;
     asm volatile("" : "+s"(nc));
     if (k >= nc) return;
-    const int tt = fresh_lane();
+    // the pivot's lane predicates (lane == k, lane == k + 1, lane <= k) are
+    // constants of k: 64-bit lane masks in SGPRs as the select conditions, no
+    // per-pivot lane index and no vector compares
+    const bool is_k = __builtin_amdgcn_inverse_ballot_w64(1ull << k);
     lsync();
     const f4v r0 = S.bc[0][0][lane & 15];
     const float v = K.k[k];
     const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
     const float pinv = __builtin_amdgcn_rcpf(p);
-    const float ng = -((tt == k) ? (1.0f - pinv) : v * pinv);
+    const float ng = -(is_k ? (1.0f - pinv) : v * pinv);
     if constexpr (k + 1 < 60) {  // unconditional (harmless past the last pivot): no branch to join
+      const bool is_k1 = __builtin_amdgcn_inverse_ballot_w64(1ull << (k + 1));
+      const bool upto_k = __builtin_amdgcn_inverse_ballot_w64((2ull << k) - 1ull);
       const float la = fmaf(dpp_col<k + 1>(r0), ng, K.k[k + 1]);
       const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, la), k + 1));
-      reinterpret_cast<float *>(&S.bc[0][0][0])[tt] = (tt == k + 1) ? p1 + 1.0f : ((tt < k + 1) ? -la : la);
+      reinterpret_cast<float *>(&S.bc[0][0][0])[lane] = is_k1 ? p1 + 1.0f : (upto_k ? -la : la);
     }
     QL_DPP_GJ60(K.k, 0, r0, ng);
-    if (p > kGjExactPivot) K.k[k] = (tt == k) ? pinv : ng;
+    if (p > kGjExactPivot) K.k[k] = is_k ? pinv : ng;
   });
   lsync();
 }
@@ -893,12 +898,8 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         r[5] = fmaxf(r[5], fabsf(px[h]));
       }
     }
-#pragma unroll
-    for (int k = 0; k < 6; ++k) o[k] = wmax_nonneg(o[k]);
-    if (want_r) {
-#pragma unroll
-      for (int k = 0; k < 6; ++k) r[k] = wmax_nonneg(r[k]);
-    }
+    wmax_nonneg6(o);
+    if (want_r) wmax_nonneg6(r);
     if constexpr (W == 2) {  // block maxima (r only where the rho estimate needs them)
       float v[12];
 #pragma unroll
@@ -1095,13 +1096,10 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
       const float rho = uf(S.sc[wv].rho), cinv = uf(S.sc[wv].cinv), sigma = uf(S.sc[wv].sigma);
       QL_LIT_LANE_INDICES(lxf);
       // this lane's row of W0^-1 for slot h (W0 = D^-1 (sigma I + A~' rho A~) D^-1 +
-      // c R, 3 x 3 per leg): written for the U rows, recomputed for the
-      // iteration coefficients after the T phase (its LDS is the T passes')
-      // (D^-1 and c re-laundered per call: the first call's copies do not stay
-      // live across S^-1 for the second)
+      // c R, 3 x 3 per leg): written to w0i for the U rows, and read back from
+      // there for the iteration coefficients after the inversion
       auto w0_inv_row = [&](int h, float &i0, float &i1, float &i2) {
-        float dinv_h = valid[h] ? 1.0f / S.dr[wv][h][lxf] : 0.0f, csw = uf(S.sc[wv].cs);
-        asm volatile("" : "+v"(dinv_h), "+v"(csw));
+        const float dinv_h = valid[h] ? 1.0f / S.dr[wv][h][lxf] : 0.0f, csw = uf(S.sc[wv].cs);
         const f4v arz = S.arz[wv][h][lxf];
         const float rv0 = eq0[h] ? 1e3f * rho : rho, rv1 = rho;
         const float d_own = rv0 * arz.x * arz.x + rv1 * arz.y * arz.y;
@@ -1190,11 +1188,22 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         // (the G^-1 tables hold the eigen axes' A_a^-1)
         const float s00 = uf(S.sc[wv].sxy[0][0]), s01 = uf(S.sc[wv].sxy[0][1]), s10 = uf(S.sc[wv].sxy[1][0]),
                     s11 = uf(S.sc[wv].sxy[1][1]);
-        const float r0 = sr == 0 ? s00 : (sr == 1 ? s10 : 0.0f), r1 = sr == 0 ? s01 : (sr == 1 ? s11 : 0.0f);
+        // padding wrench lanes (identity rows: unit entry, unit U) carry zero
+        // coefficients, so their G^-1 terms are exact zeros, and the unit entry
+        // joins the own-block addend below: one select per entry
+        const float r0 = !wvalid ? 0.0f : (sr == 0 ? s00 : (sr == 1 ? s10 : 0.0f)),
+                    r1 = !wvalid ? 0.0f : (sr == 0 ? s01 : (sr == 1 ? s11 : 0.0f));
         const float c00 = r0 * s00, c01 = r0 * s10, c10 = r1 * s01, c11 = r1 * s11;
-        const float m2 = sr == 2 ? 1.0f : 0.0f, m3 = sr == 3 ? 1.0f : 0.0f, m4 = sr == 4 ? 1.0f : 0.0f,
-                    m5 = sr == 5 ? 1.0f : 0.0f;
+        const float m2 = (wvalid && sr == 2) ? 1.0f : 0.0f, m3 = (wvalid && sr == 3) ? 1.0f : 0.0f,
+                    m4 = (wvalid && sr == 4) ? 1.0f : 0.0f, m5 = (wvalid && sr == 5) ? 1.0f : 0.0f;
         const float scale = sM * cinv;
+        // the own step block's addend per column: sM U (a valid row; fma(scale,
+        // 0, v) is v), or the padding row's whole entry fma(scale, 1, sM) on its
+        // diagonal (lanes 60 .. 63 hold no row: no unit entry)
+        const float unit = (!wvalid && ln < 60) ? 1.0f : 0.0f;
+        float own_add[6];
+#pragma unroll
+        for (int t = 0; t < 6; ++t) own_add[t] = fmaf(scale, t == sr ? unit : 0.0f, sM * Urow[t]);
 #pragma unroll
         for (int wp = 0; wp < W; ++wp) {
 #pragma unroll
@@ -1207,9 +1216,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
 #pragma unroll
             for (int t = 0; t < 6; ++t) {
               const int c = 60 * wp + 6 * k + t;
-              const bool own = wp == wv && 6 * k + t == ln;
-              const float g = wvalid ? gv[t] : (own ? 1.0f : 0.0f);
-              T.k[c] = fmaf(scale, g, blk ? sM * Urow[t] : 0.0f);
+              T.k[c] = fmaf(scale, gv[t], blk ? own_add[t] : 0.0f);
               asm volatile("" : "+v"(T.k[c]));  // final here (no sinking into the Gauss-Jordan)
             }
           }
@@ -1226,11 +1233,11 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
       // a = W0^-1 D^-1 b and x~ = D^-1 (a - W0^-1 t): this lane's row of W0^-1
       // as leg-triple shifts (D^-1 applied elementwise around the two dots)
 #pragma unroll
+      // (the rows written for U above, read back: the inversion works in
+      // S.bc and the T registers alone, so w0i still holds them)
       for (int h = 0; h < 2; ++h) {
-        float wx, wy, wz;
-        w0_inv_row(h, wx, wy, wz);
-        const f4v wi = {wx, wy, wz, 0.0f};
-        W1[h] = shift5(valid[h] ? wi.x : 0.0f, valid[h] ? wi.y : 0.0f, valid[h] ? wi.z : 0.0f, comp);
+        const float wx = S.w0i[wv][0][h][lxf], wy = S.w0i[wv][1][h][lxf], wz = S.w0i[wv][2][h][lxf];
+        W1[h] = shift5(valid[h] ? wx : 0.0f, valid[h] ? wy : 0.0f, valid[h] ? wz : 0.0f, comp);
       }
     }
     bool refactor = false;
@@ -1257,18 +1264,23 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           qvr[h] = S.qvl[wv][h][lxi];
           Dinv[h] = valid[h] ? 1.0f / S.dr[wv][h][lxi] : 0.0f;
         }
+        // rho vector (eq rows 1e3 rho) of the slots' first rows and its inverse,
+        // held for the segment (four registers; the second rows' rho is the scalar)
+        float rva0[2], rvia[2];
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+          rva0[h] = eq0[h] ? 1e3f * rho_s : rho_s;
+          rvia[h] = eq0[h] ? 1e-3f * rvb_s : rvb_s;
+          asm volatile("" : "+v"(rva0[h]), "+v"(rvia[h]));
+        }
         // wave-uniform trip count (a scalar loop, not an exec-masked one)
         iter = __builtin_amdgcn_readfirstlane(iter);
         next = __builtin_amdgcn_readfirstlane(next);
         for (; iter < next; ++iter) {
           asm volatile("" ::: "memory");
           const int par = W == 1 ? 0 : (iter & 1);  // two waves: broadcast rows double-buffered
-          // rho vector (eq rows 1e3 rho) from the scalar rho each iteration: per-lane
-          // selects instead of six loop-invariant registers
-          float rr = rho_s, rvb = rvb_s;
-          asm volatile("" : "+v"(rr), "+v"(rvb));
-          const float rva[2][2] = {{eq0[0] ? 1e3f * rr : rr, rr}, {eq0[1] ? 1e3f * rr : rr, rr}};
-          const float rvia[2] = {eq0[0] ? 1e-3f * rvb : rvb, eq0[1] ? 1e-3f * rvb : rvb};
+          const float rva[2][2] = {{rva0[0], rho_s}, {rva0[1], rho_s}};
+          const float rvb = rvb_s;
           // rhs = sigma x - q + A'(rho z - y) per slot, then a = W0^-1 D^-1 rhs
           float av[2];
 #pragma unroll
