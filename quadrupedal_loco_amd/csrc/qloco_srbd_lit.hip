@@ -198,6 +198,31 @@ __device__ __forceinline__ float tdot(float v, const Shift5 &c) {
   return a;
 }
 
+// Two independent tdots, term by term side by side (each one's operations in
+// tdot's order, so the same bits): a DPP operand is read two or more
+// instructions after it is written, and one pad covers both inputs.
+__device__ __forceinline__ void tdot2(float v0, const Shift5 &c, float v1, const Shift5 &d, float &a0, float &a1) {
+  float t0, t1, u0, u1;
+  asm("s_nop 1\n\t"
+      "v_mov_b32_dpp %2, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mov_b32_dpp %3, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mov_b32_dpp %4, %6 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mov_b32_dpp %5, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_mul_f32 %0, %6, %8\n\t"
+      "v_mul_f32 %1, %7, %13\n\t"
+      "v_fmac_f32_dpp %0, %6, %9 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %1, %7, %14 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %0, %6, %11 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %1, %7, %16 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %0, %2, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %1, %3, %15 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %0, %4, %12 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+      "v_fmac_f32_dpp %1, %5, %17 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+      : "=&v"(a0), "=&v"(a1), "=&v"(t0), "=&v"(t1), "=&v"(u0), "=&v"(u1)
+      : "v"(v0), "v"(v1), "v"(c.c0), "v"(c.cm1), "v"(c.cm2), "v"(c.cp1), "v"(c.cp2),
+        "v"(d.c0), "v"(d.cm1), "v"(d.cm2), "v"(d.cp1), "v"(d.cp2));
+}
+
 // In-place Gauss-Jordan inverse of the 60 x 60 SPD S (one row per lane,
 // pivots <= 1 after the 1/max-diagonal scaling): invert_w1's scheme (DESIGN.md
 // §3) with one pivot of look-ahead -- pivot k first applies its update to
@@ -1258,11 +1283,16 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         // across the residual checks and factorisations
         const float alpha = uf(S.sc[wv].alpha), oma = uf(S.sc[wv].oma), sigma = uf(S.sc[wv].sigma),
                     dtm = uf(S.sc[wv].dtm);
+        // (q~ and D^-1 are carried like (ra, rz) below: read again every
+        // iteration, registers only from there to the next av write, free while
+        // v = Vu a holds its operands.  D^-1 is parked in w0i, which is the
+        // factorisation's and idle between two of them.)
         float qvr[2], Dinv[2];
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           qvr[h] = S.qvl[wv][h][lxi];
           Dinv[h] = valid[h] ? 1.0f / S.dr[wv][h][lxi] : 0.0f;
+          S.w0i[wv][0][h][lxi] = Dinv[h];
         }
         // rho vector (eq rows 1e3 rho) of the slots' first rows and its inverse,
         // held for the segment (four registers; the second rows' rho is the scalar)
@@ -1276,6 +1306,21 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         // wave-uniform trip count (a scalar loop, not an exec-masked one)
         iter = __builtin_amdgcn_readfirstlane(iter);
         next = __builtin_amdgcn_readfirstlane(next);
+        // One iteration has three LDS round trips that the algorithm needs
+        // (av, the broadcast row, wv: each written and read back); every other
+        // LDS read is of data constant since the set-up and is issued where
+        // arithmetic or the matvec hides its latency:
+        //  - a slot's (ra, rz) is read once per iteration, under the second
+        //    W0^-1 product, used by update_z and carried over the back-edge
+        //    into the next iteration's rhs (read here for the segment's first);
+        //  - this lane's row of Bb is read ahead of the av write; the
+        //    variables' Bb columns, a and D^-1 under the matvec; zh and q~
+        //    under the W0^-1 products of update_x;
+        //  - the two slots' chains run stage by stage, side by side: a DPP
+        //    operand is then two instructions behind its producer.
+        __builtin_amdgcn_sched_barrier(0);  // (after the segment's index arithmetic, not among it)
+        f4v arzc[2] = {S.arz[wv][0][lxi], S.arz[wv][1][lxi]};
+        const uint64_t xym = __builtin_amdgcn_ballot_w64(xy);
         for (; iter < next; ++iter) {
           asm volatile("" ::: "memory");
           const int par = W == 1 ? 0 : (iter & 1);  // two waves: broadcast rows double-buffered
@@ -1283,57 +1328,110 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           const float rvb = rvb_s;
           // rhs = sigma x - q + A'(rho z - y) per slot, then a = W0^-1 D^-1 rhs
           float av[2];
+          float tz[2], rhs[2];
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const f4v arz = S.arz[wv][h][lxi];
-            const f2v ra = {arz.x, arz.y}, rz = {arz.z, arz.w};
+            const f2v ra = {arzc[h].x, arzc[h].y}, rz = {arzc[h].z, arzc[h].w};
             const f2v rv = {rva[h][0], rva[h][1]};
             const f2v w = __builtin_elementwise_fma(rv, z[h], -y[h]);
             const f2v aw = ra * w, zw = rz * w;
-            const float tz = zw.x + zw.y;
-            float rhs = fmaf(sigma, x[h], (aw.x + aw.y) - qvr[h]);
-            {
-              const float m2 = comp == 2 ? 1.0f : 0.0f;
-              float u;
-              asm("s_nop 1\n\t"
-                  "v_add_f32_dpp %0, %2, %2 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
-                  "s_nop 1\n\t"
-                  "v_fmac_f32_dpp %1, %0, %3 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
-                  : "=&v"(u), "+v"(rhs)
-                  : "v"(tz), "v"(m2));
-            }
-            av[h] = tdot(Dinv[h] * rhs, W1[h]);  // W0^-1 D^-1 rhs
-            S.av[wv][h][lxi] = av[h];
+            tz[h] = zw.x + zw.y;
+            rhs[h] = fmaf(sigma, x[h], (aw.x + aw.y) - qvr[h]);
           }
+          // this wrench lane's row of Bb for v = Vu a below
+          const f4v *br = reinterpret_cast<const f4v *>(S.Bb[sr]);
+          const f4v b0 = br[0], b1 = br[1], b2 = br[2];
+          __builtin_amdgcn_sched_barrier(0);
+          {
+            // both slots: rhs += [comp == 2] (tz(l - 1) + tz(l - 2)), t = D^-1 rhs,
+            // a = W0^-1 t (tdot's five terms in tdot's order)
+            // (the z rows' mask as a float: made here, not a register of the loop)
+            float m2, u0, u1, t0, t1;
+            asm volatile("v_cndmask_b32_e64 %0, 1.0, 0, %1" : "=v"(m2) : "s"(xym));
+            asm("s_nop 1\n\t"
+                "v_add_f32_dpp %2, %8, %8 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_add_f32_dpp %3, %9, %9 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "s_nop 0\n\t"
+                "v_fmac_f32_dpp %4, %2, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %5, %3, %10 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_mul_f32 %6, %11, %4\n\t"
+                "v_mul_f32 %7, %12, %5\n\t"
+                "s_nop 0\n\t"
+                "v_mov_b32_dpp %2, %6 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_mov_b32_dpp %3, %7 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_mov_b32_dpp %4, %6 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_mov_b32_dpp %5, %7 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_mul_f32 %0, %6, %13\n\t"
+                "v_mul_f32 %1, %7, %18\n\t"
+                "v_fmac_f32_dpp %0, %6, %14 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %1, %7, %19 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %0, %6, %16 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %1, %7, %21 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %0, %2, %15 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %1, %3, %20 wave_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %0, %4, %17 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0\n\t"
+                "v_fmac_f32_dpp %1, %5, %22 wave_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:0"
+                : "=&v"(av[0]), "=&v"(av[1]), "=&v"(u0), "=&v"(u1), "+v"(rhs[0]), "+v"(rhs[1]), "=&v"(t0), "=&v"(t1)
+                : "v"(tz[0]), "v"(tz[1]), "v"(m2), "v"(Dinv[0]), "v"(Dinv[1]),
+                  "v"(W1[0].c0), "v"(W1[0].cm1), "v"(W1[0].cm2), "v"(W1[0].cp1), "v"(W1[0].cp2),
+                  "v"(W1[1].c0), "v"(W1[1].cm1), "v"(W1[1].cm2), "v"(W1[1].cp1), "v"(W1[1].cp2));
+          }
+          S.av[wv][0][lxi] = av[0];
+          S.av[wv][1][lxi] = av[1];
           lsync();
           // v = Vu a: wrench row (jr, sr) over its step's 12 variables
           float wr = 0.0f;
           {
             const int hh = jr >= 5 ? 1 : 0, base = 12 * (jr - 5 * hh);
             const f4v *src = reinterpret_cast<const f4v *>(&S.av[wv][hh][base]);
-            const f4v u0 = src[0], u1 = src[1], u2 = src[2];
-            const float uv[12] = {u0.x, u0.y, u0.z, u0.w, u1.x, u1.y, u1.z, u1.w, u2.x, u2.y, u2.z, u2.w};
-            const f4v *br = reinterpret_cast<const f4v *>(S.Bb[sr]);
-            const f4v b0 = br[0], b1 = br[1], b2 = br[2];
-            const float bv[12] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x, b2.y, b2.z, b2.w};
+            // (one wave at 128 registers: the third quarter is read into the
+            // registers the first one leaves -- 20 operands live, not 24)
+            const f4v u0 = src[0], u1 = src[1];
+            f4v u2;
+            if constexpr (W == 2) u2 = src[2];
+            __builtin_amdgcn_sched_barrier(0);
             float w0 = 0.0f, w1 = 0.0f;
-#pragma unroll
-            for (int w = 0; w < 12; w += 2) {
-              w0 = fmaf(bv[w], uv[w], w0);
-              w1 = fmaf(bv[w + 1], uv[w + 1], w1);
+            w0 = fmaf(b0.x, u0.x, w0);
+            w1 = fmaf(b0.y, u0.y, w1);
+            w0 = fmaf(b0.z, u0.z, w0);
+            w1 = fmaf(b0.w, u0.w, w1);
+            if constexpr (W == 1) {
+              __builtin_amdgcn_sched_barrier(0);
+              u2 = src[2];
+              __builtin_amdgcn_sched_barrier(0);
             }
+            w0 = fmaf(b1.x, u1.x, w0);
+            w1 = fmaf(b1.y, u1.y, w1);
+            w0 = fmaf(b1.z, u1.z, w0);
+            w1 = fmaf(b1.w, u1.w, w1);
+            w0 = fmaf(b2.x, u2.x, w0);
+            w1 = fmaf(b2.y, u2.y, w1);
+            w0 = fmaf(b2.z, u2.z, w0);
+            w1 = fmaf(b2.w, u2.w, w1);
             wr = w0 + w1;
           }
           reinterpret_cast<float *>(&S.bc[par][wv][0])[lxi] = wr;
           bsync<W>();
-          // s = T v (DPP broadcast matvec, 60 columns per half)
+          // s = T v (DPP broadcast matvec, 60 columns per half); under it the
+          // reads update_x / update_z need that do not depend on s: the
+          // variable's omega rows of B_d (a padding slot's are harmless: its
+          // leg's W0^-1 coefficients are zero), a and D^-1
           float sv;
+          float bw0, bw1, bw2, zhi[2], avr[2];
           {
             const f4v r0 = S.bc[par][0][lxi & 15];
+            f4v r1;
+            if constexpr (W == 2) r1 = S.bc[par][1][lxi & 15];
+            bw0 = S.Bb[0][lxi % 12], bw1 = S.Bb[1][lxi % 12], bw2 = S.Bb[2][lxi % 12];
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              avr[h] = S.av[wv][h][lxi];  // a, as written above: read back, not held across v = Vu a
+              Dinv[h] = S.w0i[wv][0][h][lxi];
+            }
+            __builtin_amdgcn_sched_barrier(0);
             float acc0, acc1;
             QL_DPP_MATVEC60_2(acc0, acc1, r0, T.k, 0);
             if constexpr (W == 2) {
-              const f4v r1 = S.bc[par][1][lxi & 15];
               float acc2, acc3;
               QL_DPP_MATVEC60_2(acc2, acc3, r1, T.k, 60);
               sv = (acc0 + acc1) + (acc2 + acc3);
@@ -1343,22 +1441,42 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           }
           S.wv[wv][lxi] = sv;
           lsync();
-          // x~ = D^-1 a - D^-1 W0^-1 Vu' s, then update_x / update_z / update_y; the
-          // variable's omega rows of B_d from LDS (a padding slot's are harmless:
-          // its leg's B1 coefficients are zero)
-          const float bw0 = S.Bb[0][lxi % 12], bw1 = S.Bb[1][lxi % 12], bw2 = S.Bb[2][lxi % 12];
+          // x~ = D^-1 a - D^-1 W0^-1 Vu' s, then update_x / update_z / update_y:
+          // both slots' wrench triples under one wait, the chains side by side
+          f2v s01[2], s23[2], s45[2];
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             const float *gs = &S.wv[wv][6 * stepl[h]];
-            const f2v s01 = *reinterpret_cast<const f2v *>(gs), s23 = *reinterpret_cast<const f2v *>(gs + 2);
-            f2v s45 = *reinterpret_cast<const f2v *>(gs + 4);
-            asm volatile("" : "+v"(s45));  // loaded by every lane (no exec-masked load)
-            const float sf = comp == 0 ? s23.y : (comp == 1 ? s45.x : s45.y);
-            const float tv = fmaf(bw0, s01.x, fmaf(bw1, s01.y, fmaf(bw2, s23.x, dtm * sf)));
-            const float xt = Dinv[h] * (av[h] - tdot(tv, W1[h]));  // D^-1 (a - W0^-1 t)
-            const f4v arz = S.arz[wv][h][lxi];
-            const f2v ra = {arz.x, arz.y}, rz = {arz.z, arz.w};
-            const float hi = S.zh[wv][h][lxi];
+            s01[h] = *reinterpret_cast<const f2v *>(gs);
+            s23[h] = *reinterpret_cast<const f2v *>(gs + 2);
+            s45[h] = *reinterpret_cast<const f2v *>(gs + 4);
+          }
+          asm volatile("" : "+v"(s45[0]), "+v"(s45[1]));  // loaded by every lane (no exec-masked load)
+          float tv[2], td[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const float f0 = s23[h].y, f1 = s45[h].x, f2 = s45[h].y;
+            const float sf = comp == 0 ? f0 : (comp == 1 ? f1 : f2);
+            tv[h] = fmaf(bw0, s01[h].x, fmaf(bw1, s01[h].y, fmaf(bw2, s23[h].x, dtm * sf)));
+          }
+          // (ra, rz) for update_z and the next iteration's rhs: into the registers
+          // the wrench triples leave, under the two W0^-1 products
+          asm volatile("" : "+v"(tv[0]), "+v"(tv[1]));
+          arzc[0] = S.arz[wv][0][lxi];
+          arzc[1] = S.arz[wv][1][lxi];
+          __builtin_amdgcn_sched_barrier(0);
+          tdot2(tv[0], W1[0], tv[1], W1[1], td[0], td[1]);
+          // the upper bounds, and q~ for the next iteration's rhs
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            zhi[h] = S.zh[wv][h][lxi];
+            qvr[h] = S.qvl[wv][h][lxi];
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const float xt = Dinv[h] * (avr[h] - td[h]);  // D^-1 (a - W0^-1 t)
+            const f2v ra = {arzc[h].x, arzc[h].y}, rz = {arzc[h].z, arzc[h].w};
+            const float hi = zhi[h];
             const f2v bnd = {xy ? 0.0f : zlo * hi, hi};
             const float n1 = lane_next(xt), n2 = lane_next(n1);
             const float xtz = comp == 0 ? n2 : n1;

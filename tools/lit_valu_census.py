@@ -11,10 +11,16 @@ for the phase of the last srbd_lit_one line seen before them, so the split
 between neighbouring phases is approximate where the scheduler interleaves
 them; the kernel totals and the resource lines are exact.
 
+For the ADMM inner loop alone (the innermost loop that holds the DPP matvec
+and ends in a scalar back-edge: one iteration, executed as counted) it also
+prints the VALU instructions, the LDS reads by width, the LDS writes, the
+s_waitcnt that wait on lgkmcnt and the s_nop.
+
   python tools/lit_valu_census.py [--src FILE] [--asm FILE] [--tag TEXT]
 
 --asm reads an existing assembly file (made with -gline-tables-only)."""
 import argparse
+import collections
 import os
 import re
 import subprocess
@@ -129,6 +135,44 @@ def census(asm, src):
     return names, kernels, meta
 
 
+def inner_loop(asm):
+    """{kernel: counts of the ADMM iteration's loop body}: the block from the
+    last label before the 60-column matvec's first row_newbcast:14 operand that
+    follows an `s_cbranch_scc1` back to that label."""
+    lines = open(asm).read().split("\n")
+    res, cur = {}, None
+    for i, ln in enumerate(lines):
+        m = re.match(r"(_ZN5qloco\w+):", ln)
+        if m and "kernel" in m.group(1):
+            cur = m.group(1)
+            continue
+        m = re.match(r"\s+s_cbranch_scc1\s+(\.LBB\d+_\d+)", ln)
+        if not (m and cur) or cur in res:
+            continue
+        top = next((j for j in range(i, -1, -1) if lines[j].startswith(m.group(1) + ":")), None)
+        body = [x.strip() for x in lines[top:i + 1]] if top is not None else []
+        if sum("row_newbcast:14" in x for x in body) < 4 or any(re.match(r"\.LBB\d+_\d+:", x) for x in body[1:]):
+            continue
+        c = collections.OrderedDict((k, 0) for k in (
+            "VALU", "LDS read b128", "LDS read other", "LDS write", "s_waitcnt lgkmcnt", "s_nop", "scratch"))
+        for x in body:
+            op = x.split()[0] if x.split() else ""
+            if op.startswith("v_"):
+                c["VALU"] += 1
+            elif op.startswith("ds_read"):
+                c["LDS read b128" if op == "ds_read_b128" else "LDS read other"] += 1
+            elif op.startswith("ds_write"):
+                c["LDS write"] += 1
+            elif op == "s_waitcnt" and "lgkmcnt" in x:
+                c["s_waitcnt lgkmcnt"] += 1
+            elif op == "s_nop":
+                c["s_nop"] += 1
+            elif op.startswith("scratch_"):
+                c["scratch"] += 1
+        res[cur] = c
+    return res
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--src", default=SRC)
@@ -142,6 +186,7 @@ def main():
         asm = os.path.join(tmp, "lit.s")
         compile_asm(a.src, asm)
     names, kernels, meta = census(asm, a.src)
+    loops = inner_loop(asm)
     print("# literal SRBD kernels: static instruction census %s" % a.tag)
     print("# (static counts per phase of srbd_lit_one; 64-bit VALU counted apart and included in VALU)")
     for k in sorted(kernels):
@@ -160,6 +205,8 @@ def main():
             for key in tot:
                 tot[key] += row[key]
         print("  %-34s %7d %7d %6d %6d %6d" % ("total", tot["valu"], tot["f64"], tot["lds"], tot["nop"], tot["vmem"]))
+        if k in loops:
+            print("  ADMM inner loop, one iteration: " + ", ".join("%s %d" % kv for kv in loops[k].items()))
     if tmp:
         os.remove(asm)
         os.rmdir(tmp)
