@@ -738,6 +738,84 @@ int qloco_a1_ctrl_joint_torques(const qloco_a1_ctrl_params *prm, int64_t batch, 
 int qloco_a1_ctrl_get_state(int64_t batch, const void *workspace, double *state, void *stream);
 int qloco_a1_ctrl_set_state(int64_t batch, void *workspace, const double *state, void *stream);
 
+/* ====================================================================== */
+/* 14. slow planner's step-timing SQP, batched (fp64)                      */
+/*    replaces NLPClass::step_timing_opti_loop (unitree_ros/mosek_nlp_kmp/ */
+/*    src/NLP/NLPClass_sqp.cpp:693-1102) with the parts of FootStepInputs / */
+/*    Initialize it reads (:51-77, :131-138, :160-206, :212-216, :243-306), */
+/*    Indexfind (:1105-1141), step_timing_object_function (:1144-1173),     */
+/*    step_timing_constraints (:1175-1458) and solve_stepping_timing        */
+/*    (:1619-1638): three SQP passes over a QP with 4 variables, 1 equality */
+/*    and 24 inequalities (EiQuadProg), then the _ts / _tx / foot-location  */
+/*    / CoM boundary-state updates and three samples of the LIP CoM.  The   */
+/*    producer of the ts / tx inputs of section 8.  Not computed:           */
+/*    CoM_height_solve (:2361) and with it _comz, ZMP and DCM; the          */
+/*    _nTdx > 3 tail of the CoM roll-out; Foot_trajectory_solve; KMP.       */
+/* ====================================================================== */
+/* Defaults: NLPClass.h:32-37, the "go1" branch of Initialize (:243-306) and
+ * the robot constants NLPRTControlClass.cpp:33-56 passes (FOOT_WIDTH = 0.03
+ * there, not the 0.01 of robot_const_para_config.cpp). */
+typedef struct qloco_nlp_params {
+  double dt, tstep;                 /* 0.025, 0.7 */
+  double t_min, t_max;              /* 0.5, 1 */
+  double footx_vmax, footx_vmin, footy_vmax, footy_vmin; /* 3, -2.875, 2, -1 */
+  double comax_max, comax_min, comay_max, comay_min;     /* 5, -5, 6, -6 */
+  double aax, aay, aaxv, aayv, bbx, bby, rr1, rr2;       /* objective weights */
+  double footx_max, footx_min;      /* 0.15, -0.05 */
+  double z_c, g, half_hip_width, foot_width; /* 0.309458, 9.8, 0.12675, 0.03 */
+  double lamda_comx, lamda_comvx, lamda_comy, lamda_comvy; /* feedback blend (:980-983), 0 */
+  double reserved[2];
+} qloco_nlp_params;
+void qloco_nlp_params_default(qloco_nlp_params *p);
+/* Every robot's members live in a device workspace of
+ * qloco_nlp_workspace_bytes(batch) bytes (-1 for batch <= 0).  Its first
+ * 2 * B * 27 doubles are ts[B*27] then tx[B*27], a row per robot: the arrays
+ * qloco_support_phase takes, so the two calls chain with no copy.  The rest is
+ * field-major.  get_state / set_state move a dense record of QLOCO_NLP_STATE
+ * doubles per robot:
+ *   [0:27] _ts | [27:54] _tx | [54:81] _td | [81:108] _Lxx_ref |
+ *   [108:135] _Lyy_ref | [135:162] _footx_ref | [162:189] _footy_ref |
+ *   [189:216] _COMx_is | [216:243] _COMvx_is | [243:270] _COMy_is |
+ *   [270:297] _COMvy_is | [297:301] _Vari_ini.col(i-1) |
+ *   [301:307] _comx/_comvx/_comax/_comy/_comvy/_comay _feed(i-1) |
+ *   [307:309] _comvx_endref, _comvy_endref */
+#define QLOCO_NLP_STATE 309
+/* per-pass code beside the qloco_status values of the solver, and the
+ * per-robot status of a robot whose _periond_i would pass 26 */
+#define QLOCO_NLP_SKIPPED (-1)
+#define QLOCO_NLP_FINISHED (-2)
+int64_t qloco_nlp_workspace_bytes(int64_t batch);
+/* FootStepInputs + Initialize for B robots: steplength[B], stepwidth[B]
+ * (device; the reference passes 0.075 and 2 * half_hip_width); stepheight[B]
+ * is optional (it only reaches _footz_ref, which the SQP never reads). */
+int qloco_nlp_init(const qloco_nlp_params *prm, int64_t batch, void *workspace,
+                   const double *steplength, const double *stepwidth, const double *stepheight,
+                   void *stream);
+/* One planner tick of every robot.  Device pointers: t_int[B] (int32, the
+ * loop index i >= 1), estimated_state[B*6] (elements 0..5), rfoot_feedback /
+ * lfoot_feedback[B*2] (x, y).  Outputs: vari_ini[B*4] required; optional
+ * (NULL): sched[B*4] (int32: _periond_i, _k_yu, _bjxx, _bjx1), step[B*3]
+ * (_ts(_periond_i-1), _Lxx_ref(_periond_i-1), _Lyy_ref(_periond_i-1) after the
+ * update), com[B*18] (for i, i+1, i+2: comx, comy, comvx, comvy, comax,
+ * comay), pass_status / pass_iters[B*3] (per SQP pass: the EiQuadProg outcome
+ * -- QLOCO_INFEASIBLE's partial iterate is added, as the reference does -- or
+ * QLOCO_NLP_SKIPPED, and the iteration count), status[B]: QLOCO_OK, QLOCO_NAN
+ * (a non-finite result, carried into the record), QLOCO_NLP_FINISHED or
+ * QLOCO_BAD_SIZE (i < 1 or before the plan); the last two leave the record
+ * untouched and return NaN. */
+int qloco_nlp_step_timing(const qloco_nlp_params *prm, int64_t batch, void *workspace,
+                          const int32_t *t_int, const double *estimated_state,
+                          const double *rfoot_feedback, const double *lfoot_feedback,
+                          double *vari_ini, int32_t *sched, double *step, double *com,
+                          int32_t *pass_status, int32_t *pass_iters, int32_t *status,
+                          void *stream);
+/* Dense state[B * QLOCO_NLP_STATE] out of / into the workspace. */
+int qloco_nlp_get_state(int64_t batch, const void *workspace, double *state, void *stream);
+int qloco_nlp_set_state(int64_t batch, void *workspace, const double *state, void *stream);
+/* Lanes per robot of the tick kernel: 4 (default), 8 or 16; results do not
+ * depend on it.  Returns the previous width, or QLOCO_ERR_ARG. */
+int qloco_nlp_set_group_width(int gw);
+
 #ifdef __cplusplus
 }
 #endif

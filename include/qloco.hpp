@@ -24,6 +24,8 @@
  *                                    preamble of compute_grf (:341-380)
  *   A1BasicEKFBatch               <- A1BasicEKF (a1_cpp_open_source/src/A1BasicEKF.h:25-72;
  *                                    GazeboA1ROS.cpp:204-209)
+ *   NLPStepTimingBatch            <- NLPClass::step_timing_opti_loop (mosek_nlp_kmp/src/NLP/
+ *                                    NLPClass_sqp.cpp:693-1102; NLPRTControlClass.cpp:445)
  *   Kinematicclass                <- go1_rt_control Kinematicclass
  *                                    (Kinematics.h:30-61; servo.cpp:734-741, :1038-1051)
  *   ServoForceBlock               <- the go1 servo loop's force block (servo.cpp:1052-1243)
@@ -380,6 +382,54 @@ class A1RobotControlBatch {
   double *d_in_, *d_out_, *d_rec_;
   int32_t *d_mode_;
   uint8_t *d_ct_;
+};
+
+// ------------------------------------------------------------------------
+// NLPClass::step_timing_opti_loop (mosek_nlp_kmp/src/NLP/NLPClass.h:66-67,
+// NLPClass_sqp.cpp:693-1102; called at NLPRTControlClass.cpp:445) for B robots
+// -> qloco_nlp_step_timing.  The constructor runs FootStepInputs + Initialize.
+// estimated_state is the reference's 18-vector (elements 0..5 are read), the
+// foot-location feedbacks its 3-vectors (x, y are read); `lamda` and
+// `stopwalking` are accepted and unused, as in the reference (they only reach
+// CoM_height_solve).  The 38-vector com_traj comes back per robot (row per
+// robot, the reference's slot order).  Slots this library does not compute --
+// _comz / _comvz / _comaz and everything derived from them, ZMP and DCM:
+// 2, 5, 8, 9..20, 23, 26 -- are quiet NaN on every call, never stale.  Slots
+// 28..33 are NaN too on the plan's last step, where the reference reads
+// _footx_ref past its end.
+class NLPStepTimingBatch {
+ public:
+  static constexpr int kComTraj = 38;
+  NLPStepTimingBatch(int batch, double stepwidth, double steplength, double stepheight,
+                     const qloco_nlp_params *params = nullptr);
+  // B = 1: the reference's signature, returns com_traj
+  std::array<double, 38> step_timing_opti_loop(int i, const double estimated_state[18],
+                                               const double Rfoot_location_feedback[3],
+                                               const double Lfoot_location_feedback[3], double lamda,
+                                               bool stopwalking);
+  // B robots: estimated_state[B*18], feedbacks[B*3] -> com_traj[B*38]
+  void step_timing_opti_loop(int i, const double *estimated_state, const double *Rfoot_location_feedback,
+                             const double *Lfoot_location_feedback, double lamda, bool stopwalking,
+                             double *com_traj);
+  // dense member state, B * QLOCO_NLP_STATE doubles (include/qloco.h section 14)
+  void get_state(double *state);
+  void set_state(const double *state);
+  // of the last call, per robot: QLOCO_OK, QLOCO_NAN, QLOCO_NLP_FINISHED, QLOCO_BAD_SIZE
+  const std::vector<int32_t> &status() const { return status_; }
+  // device views for qloco_support_phase: _ts / _tx, B x 27 doubles each
+  const double *ts_device() const { return (const double *)d_ws_; }
+  const double *tx_device() const { return (const double *)d_ws_ + (size_t)batch_ * QLOCO_NLP_STEPS; }
+  qloco_nlp_params params;
+  int batch() const { return batch_; }
+
+ private:
+  int batch_;
+  double stepheight_;
+  DeviceArena arena_;
+  void *d_ws_;
+  double *d_in_, *d_out_, *d_rec_;
+  int32_t *d_i_, *d_int_;
+  std::vector<int32_t> status_;
 };
 
 // ------------------------------------------------------------------------

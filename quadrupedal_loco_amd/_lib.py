@@ -78,6 +78,15 @@ class A1CtrlParams(C.Structure):
                 ("reserved", C.c_int32 * 5)]
 
 
+class NlpParams(C.Structure):
+    """Mirror of `qloco_nlp_params`."""
+    _fields_ = [(k, C.c_double) for k in (
+        "dt", "tstep", "t_min", "t_max", "footx_vmax", "footx_vmin", "footy_vmax", "footy_vmin",
+        "comax_max", "comax_min", "comay_max", "comay_min", "aax", "aay", "aaxv", "aayv", "bbx", "bby",
+        "rr1", "rr2", "footx_max", "footx_min", "z_c", "g", "half_hip_width", "foot_width",
+        "lamda_comx", "lamda_comvx", "lamda_comy", "lamda_comvy")] + [("reserved", C.c_double * 2)]
+
+
 vp = C.c_void_p
 i64 = C.c_int64
 i32 = C.c_int32
@@ -145,6 +154,13 @@ SIGNATURES = {
     "qloco_a1_ctrl_joint_torques": (C.c_int, [C.POINTER(A1CtrlParams), i64] + [vp] * 5),
     "qloco_a1_ctrl_get_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_a1_ctrl_set_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_params_default": (None, [C.POINTER(NlpParams)]),
+    "qloco_nlp_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_nlp_init": (C.c_int, [C.POINTER(NlpParams), i64] + [vp] * 5),
+    "qloco_nlp_step_timing": (C.c_int, [C.POINTER(NlpParams), i64] + [vp] * 13),
+    "qloco_nlp_get_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_set_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_set_group_width": (C.c_int, [C.c_int]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),
     "qloco_mgpu_gather_rows": (C.c_int, [i64, i32, i32, vp]),
     "qloco_mgpu_reorder": (C.c_int, [i64, i32, i32, i32, vp, vp, vp, vp, vp]),

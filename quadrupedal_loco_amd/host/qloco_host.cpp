@@ -13,6 +13,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <limits>
 
 namespace qloco {
 
@@ -850,6 +851,132 @@ void A1RobotControlBatch::get_state(double *state) {
   arena_.sync();
 }
 
+
+// ------------------------------------------------------------------------
+// NLPStepTimingBatch -> qloco_nlp_*
+namespace {
+// device input block, per robot: est[6] | rfoot[2] | lfoot[2]; output block:
+// vari[4] | step[3] | com[18]; int block: sched[4] | status[1]
+constexpr size_t kNI_EST = 0, kNI_RF = 6, kNI_LF = 8, kNI_N = 10;
+constexpr size_t kNO_VARI = 0, kNO_STEP = 4, kNO_COM = 7, kNO_N = 25;
+}  // namespace
+
+NLPStepTimingBatch::NLPStepTimingBatch(int batch, double stepwidth, double steplength, double stepheight,
+                                       const qloco_nlp_params *p)
+    : batch_(positive_batch(batch, "NLPStepTimingBatch")), stepheight_(stepheight) {
+  if (p) params = *p;
+  else qloco_nlp_params_default(&params);
+  const size_t B = batch;
+  const int64_t ws = qloco_nlp_workspace_bytes(batch);
+  if (ws < 0) throw Error("qloco_nlp_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_in_ = dalloc<double>(arena_, B * kNI_N);
+  d_out_ = dalloc<double>(arena_, B * kNO_N);
+  d_rec_ = dalloc<double>(arena_, B * QLOCO_NLP_STATE);
+  d_i_ = dalloc<int32_t>(arena_, B);
+  d_int_ = dalloc<int32_t>(arena_, B * 5);
+  status_.assign(B, QLOCO_OK);
+  std::vector<double> in(2 * B);
+  for (size_t b = 0; b < B; ++b) {
+    in[b] = steplength;
+    in[B + b] = stepwidth;
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  abi_ok(qloco_nlp_init(&params, batch_, d_ws_, d_in_, d_in_ + B, nullptr, arena_.stream()), "qloco_nlp_init");
+  arena_.sync();
+}
+
+void NLPStepTimingBatch::step_timing_opti_loop(int i, const double *est, const double *rfoot, const double *lfoot,
+                                               double /*lamda*/, bool /*stopwalking*/, double *com_traj) {
+  if (!est || !rfoot || !lfoot || !com_traj)
+    throw Error("NLPStepTimingBatch::step_timing_opti_loop: null argument", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  std::vector<double> in(B * kNI_N);
+  std::vector<int32_t> ti(B, i);
+  for (size_t b = 0; b < B; ++b) {
+    for (int k = 0; k < 6; ++k) in[kNI_EST * B + 6 * b + k] = est[18 * b + k];
+    for (int k = 0; k < 2; ++k) {
+      in[kNI_RF * B + 2 * b + k] = rfoot[3 * b + k];
+      in[kNI_LF * B + 2 * b + k] = lfoot[3 * b + k];
+    }
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  arena_.upload(d_i_, ti.data(), sizeof(int32_t) * B);
+  abi_ok(qloco_nlp_step_timing(&params, batch_, d_ws_, d_i_, d_in_ + kNI_EST * B, d_in_ + kNI_RF * B,
+                               d_in_ + kNI_LF * B, d_out_ + kNO_VARI * B, d_int_, d_out_ + kNO_STEP * B,
+                               d_out_ + kNO_COM * B, nullptr, nullptr, d_int_ + 4 * B, arena_.stream()),
+         "qloco_nlp_step_timing");
+  abi_ok(qloco_nlp_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_get_state");
+  std::vector<double> out(B * kNO_N), rec(B * QLOCO_NLP_STATE);
+  std::vector<int32_t> ints(B * 5);
+  arena_.download(out.data(), d_out_, sizeof(double) * out.size());
+  arena_.download(rec.data(), d_rec_, sizeof(double) * rec.size());
+  arena_.download(ints.data(), d_int_, sizeof(int32_t) * ints.size());
+  arena_.sync();
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  for (size_t b = 0; b < B; ++b) {
+    double *c = com_traj + kComTraj * b;
+    for (int k = 0; k < kComTraj; ++k) c[k] = nan;  // 2, 5, 8, 9..20, 23, 26 stay NaN
+    status_[b] = ints[4 * B + b];
+    if (status_[b] != QLOCO_OK && status_[b] != QLOCO_NAN) continue;
+    const double *com = &out[kNO_COM * B + 18 * b], *step = &out[kNO_STEP * B + 3 * b];
+    const double *fx = &rec[QLOCO_NLP_STATE * b + 135], *fy = &rec[QLOCO_NLP_STATE * b + 162];
+    const int period = ints[4 * b + 0], bjxx = ints[4 * b + 2];
+    c[0] = com[0];  // :1048-1056
+    c[1] = com[1];
+    c[3] = com[2];
+    c[4] = com[3];
+    c[6] = com[4];
+    c[7] = com[5];
+    c[21] = com[6 + 4];  // :1072-1077
+    c[22] = com[6 + 5];
+    c[24] = com[12 + 4];
+    c[25] = com[12 + 5];
+    c[27] = bjxx;  // :1079-1090
+    if (bjxx >= 0 && bjxx + 1 < QLOCO_NLP_STEPS) {
+      c[28] = fx[bjxx];
+      c[29] = fx[bjxx + 1];
+      c[30] = fy[bjxx];
+      c[31] = fy[bjxx + 1];
+      // _footz_ref(k) = k * stepheight accumulated as the reference does (:180)
+      double z = 0.0, z0 = 0.0, z1 = 0.0;
+      for (int k = 0; k <= bjxx + 1; ++k) {
+        if (k == bjxx) z0 = z;
+        if (k == bjxx + 1) z1 = z;
+        z = z + stepheight_;
+      }
+      c[32] = z0;
+      c[33] = z1;
+    }
+    c[34] = period - 1;
+    c[35] = step[0];
+    c[36] = step[1];
+    c[37] = step[2];
+  }
+}
+
+std::array<double, 38> NLPStepTimingBatch::step_timing_opti_loop(int i, const double estimated_state[18],
+                                                                 const double Rfoot[3], const double Lfoot[3],
+                                                                 double lamda, bool stopwalking) {
+  if (batch_ != 1) throw Error("NLPStepTimingBatch: the single-robot call needs batch 1", QLOCO_ERR_ARG);
+  std::array<double, 38> r;
+  step_timing_opti_loop(i, estimated_state, Rfoot, Lfoot, lamda, stopwalking, r.data());
+  return r;
+}
+
+void NLPStepTimingBatch::get_state(double *state) {
+  if (!state) throw Error("NLPStepTimingBatch::get_state: null output", QLOCO_ERR_ARG);
+  abi_ok(qloco_nlp_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_get_state");
+  arena_.download(state, d_rec_, sizeof(double) * (size_t)batch_ * QLOCO_NLP_STATE);
+  arena_.sync();
+}
+
+void NLPStepTimingBatch::set_state(const double *state) {
+  if (!state) throw Error("NLPStepTimingBatch::set_state: null input", QLOCO_ERR_ARG);
+  arena_.upload(d_rec_, state, sizeof(double) * (size_t)batch_ * QLOCO_NLP_STATE);
+  abi_ok(qloco_nlp_set_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_set_state");
+  arena_.sync();
+}
 
 // ------------------------------------------------------------------------
 // Kinematicclass -> qloco_leg_fk / qloco_leg_ik

@@ -1,0 +1,141 @@
+"""Batched step-timing SQP of the slow gait planner (fp64) on gfx950.
+
+Python mirror of NLPClass::step_timing_opti_loop of the Go1 planner node
+(unitree_ros/mosek_nlp_kmp/src/NLP/NLPClass_sqp.cpp:693-1102): per 40 Hz tick
+and robot, three SQP passes over a QP with 4 variables (next step length and
+width, cosh / sinh of the remaining step time), 1 equality and 24
+inequalities, then the _ts / _tx / foot-location / CoM boundary-state updates
+and the LIP CoM at i, i + 1, i + 2 -- `qloco_nlp_step_timing`, one fused
+kernel (csrc/qloco_nlp.hip).  There is no host fallback.
+
+Every robot's members live in a device workspace.  `ts` and `tx` are (B, 27)
+views of it in the layout `qloco_support_phase` takes, so
+
+    out = planner.tick(t_int, est, rfoot, lfoot)
+    rt.support_phase(planner.ts, planner.tx, t_int, t_end)
+
+chains on one stream with no copy.  Not computed: CoM_height_solve (and with
+it _comz, ZMP, DCM), the foot trajectories and KMP.
+"""
+import ctypes as C
+from dataclasses import dataclass
+
+from ._lib import NlpParams, check, lib, ptr
+from .a1est import _dev
+
+NS = 27               # QLOCO_NLP_STEPS
+STATE = 309           # QLOCO_NLP_STATE
+SKIPPED, FINISHED = -1, -2   # QLOCO_NLP_SKIPPED, QLOCO_NLP_FINISHED
+STATE_FIELDS = dict(  # slices of the dense record get_state / set_state use
+    ts=(0, 27), tx=(27, 54), td=(54, 81), Lxx_ref=(81, 108), Lyy_ref=(108, 135), footx_ref=(135, 162),
+    footy_ref=(162, 189), COMx_is=(189, 216), COMvx_is=(216, 243), COMy_is=(243, 270),
+    COMvy_is=(270, 297), vari=(297, 301), feed=(301, 307), endref=(307, 309))
+
+
+def default_params(**overrides):
+    """NLPClass.h:32-37, the "go1" branch of Initialize and the constants
+    NLPRTControlClass.cpp:33-56 passes."""
+    p = NlpParams()
+    lib().qloco_nlp_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k == "reserved" or not hasattr(p, k):
+            raise ValueError("unknown parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+@dataclass
+class StepTimingResult:
+    vari_ini: object      # (B, 4): Lxx, Lyy, tr1, tr2 after the three passes
+    sched: object         # (B, 4) int32: _periond_i, _k_yu, _bjxx, _bjx1
+    step: object          # (B, 3): _ts, _Lxx_ref, _Lyy_ref of step _periond_i - 1
+    com: object           # (B, 18): i, i+1, i+2 x (comx, comy, comvx, comvy, comax, comay)
+    pass_status: object   # (B, 3) int32: EiQuadProg outcome per pass, or SKIPPED
+    pass_iters: object    # (B, 3) int32
+    status: object        # (B,) int32: 0, QLOCO_NAN (3), QLOCO_BAD_SIZE (4) or FINISHED
+
+
+class StepTimingPlanner:
+    """Batched drop-in for NLPClass's step-timing optimisation: one set of
+    members per robot, resident on the device."""
+
+    def __init__(self, batch, device, params=None, steplength=0.075, stepwidth=None, **overrides):
+        import torch
+        if batch < 1:
+            raise ValueError("batch < 1")
+        self.batch = int(batch)
+        self.device = torch.device(device)
+        self.params = params if params is not None else default_params(**overrides)
+        nbytes = lib().qloco_nlp_workspace_bytes(self.batch)
+        if nbytes <= 0:
+            raise ValueError("qloco_nlp_workspace_bytes(%d) = %d" % (self.batch, nbytes))
+        self.workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.device)
+        B = self.batch
+        self.ts = self.workspace[:B * NS].view(B, NS)            # _ts, a row per robot
+        self.tx = self.workspace[B * NS:2 * B * NS].view(B, NS)  # _tx
+        if stepwidth is None:
+            stepwidth = 2 * self.params.half_hip_width
+        self.init(steplength, stepwidth)
+
+    def _stream(self, stream):
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream
+                          if stream is None else stream)
+
+    def _f64(self, *shape):
+        import torch
+        return torch.empty(shape, dtype=torch.float64, device=self.device)
+
+    def _per_robot(self, v, name):
+        import torch
+        if not torch.is_tensor(v):
+            v = torch.as_tensor(v, dtype=torch.float64).expand(self.batch).contiguous().to(self.device)
+        return _dev(v, "f64", (self.batch,), name)
+
+    def init(self, steplength, stepwidth, stream=None):
+        """FootStepInputs + Initialize: scalars or per-robot (B,) values."""
+        sl = self._per_robot(steplength, "steplength")
+        sw = self._per_robot(stepwidth, "stepwidth")
+        check(lib().qloco_nlp_init(C.byref(self.params), self.batch, ptr(self.workspace), ptr(sl), ptr(sw),
+                                   None, self._stream(stream)), "qloco_nlp_init")
+
+    def tick(self, t_int, estimated_state, rfoot_feedback, lfoot_feedback, out=None, stream=None):
+        """One planner tick: t_int (B,) int32, estimated_state (B, 6),
+        rfoot_feedback / lfoot_feedback (B, 2), device tensors."""
+        import torch
+        B = self.batch
+        _dev(t_int, "i32", (B,), "t_int")
+        _dev(estimated_state, "f64", (B, 6), "estimated_state")
+        _dev(rfoot_feedback, "f64", (B, 2), "rfoot_feedback")
+        _dev(lfoot_feedback, "f64", (B, 2), "lfoot_feedback")
+        if out is None:
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)
+            out = StepTimingResult(self._f64(B, 4), i32(B, 4), self._f64(B, 3), self._f64(B, 18), i32(B, 3),
+                                   i32(B, 3), i32(B))
+        check(lib().qloco_nlp_step_timing(
+            C.byref(self.params), B, ptr(self.workspace), ptr(t_int), ptr(estimated_state),
+            ptr(rfoot_feedback), ptr(lfoot_feedback), ptr(out.vari_ini), ptr(out.sched), ptr(out.step),
+            ptr(out.com), ptr(out.pass_status), ptr(out.pass_iters), ptr(out.status),
+            self._stream(stream)), "qloco_nlp_step_timing")
+        return out
+
+    def get_state(self, stream=None):
+        """Dense (B, 309) record per robot (STATE_FIELDS)."""
+        s = self._f64(self.batch, STATE)
+        check(lib().qloco_nlp_get_state(self.batch, ptr(self.workspace), ptr(s), self._stream(stream)),
+              "qloco_nlp_get_state")
+        return s
+
+    def set_state(self, state, stream=None):
+        _dev(state, "f64", (self.batch, STATE), "state")
+        check(lib().qloco_nlp_set_state(self.batch, ptr(self.workspace), ptr(state), self._stream(stream)),
+              "qloco_nlp_set_state")
+
+
+def set_group_width(gw):
+    """Lanes per robot of the tick kernel (4, 8 or 16); returns the previous
+    width.  A throughput knob: results do not depend on it."""
+    r = lib().qloco_nlp_set_group_width(int(gw))
+    if r == 100:
+        raise ValueError("group width must be 4, 8 or 16")
+    return r
