@@ -751,6 +751,7 @@ int qloco_a1_ctrl_set_state(int64_t batch, void *workspace, const double *state,
 /*    producer of the ts / tx inputs of section 8.  Not computed:           */
 /*    CoM_height_solve (:2361) and with it _comz, ZMP and DCM; the          */
 /*    _nTdx > 3 tail of the CoM roll-out; Foot_trajectory_solve; KMP.       */
+/*    Section 15 adds CoM_height_solve, ZMP / DCM and the swing feet.       */
 /* ====================================================================== */
 /* Defaults: NLPClass.h:32-37, the "go1" branch of Initialize (:243-306) and
  * the robot constants NLPRTControlClass.cpp:33-56 passes (FOOT_WIDTH = 0.03
@@ -815,6 +816,82 @@ int qloco_nlp_set_state(int64_t batch, void *workspace, const double *state, voi
 /* Lanes per robot of the tick kernel: 4 (default), 8 or 16; results do not
  * depend on it.  Returns the previous width, or QLOCO_ERR_ARG. */
 int qloco_nlp_set_group_width(int gw);
+
+/* ====================================================================== */
+/* 15. the rest of the slow planner's tick, batched (fp64)                 */
+/*    completes section 14 up to the NLPClass boundary: CoM_height_solve   */
+/*    (NLPClass_sqp.cpp:2361-2473, called at :936 with the _bjx1 of the     */
+/*    previous tick) and with it _comz / _comvz / _comaz, the ZMP and DCM   */
+/*    samples (:950-954, _Zsc of :323-328), all 38 slots of com_traj        */
+/*    (:1048-1090) and Foot_trajectory_solve_mod2 (:2039-2358) with         */
+/*    solve_AAA_inv2 (:3633-3644).  One call launches section 14's kernel   */
+/*    unchanged and then one kernel of its own on the same stream.  Not     */
+/*    computed: Zmp_distributor / Force_torque_calculate, the               */
+/*    _state_generate_interpo packing, KMP and foot rotation, the unused    */
+/*    Foot_trajectory_solve, the _nTdx > 3 tail.                            */
+/* ====================================================================== */
+/* Defaults: _lift_height = 0.03 (NLPRTControlClass.cpp:48); _hcom =
+ * RobotPara_Z_C - _height_offset = 0.309458 (NLPClass_sqp.cpp:212,
+ * NLPClass.h:37, robot_const_para_config.cpp:14). */
+typedef struct qloco_nlp_tick_params {
+  double lift_height, hcom;
+  double reserved[6];
+} qloco_nlp_tick_params;
+void qloco_nlp_tick_params_default(qloco_nlp_tick_params *p);
+/* The members section 14's record lacks live in a second device workspace of
+ * qloco_nlp_tick_workspace_bytes(batch) bytes (-1 for batch <= 0), field-major
+ * (field f of robot b at f * B + b), followed by scratch for the step-timing
+ * outputs the caller does not ask for.  get_state / set_state move a dense
+ * record of QLOCO_NLP_TICK_STATE doubles per robot (integers as doubles):
+ *   [0] _bjx1 of the previous tick | [1] _ry_left_right | [2] _t_end_footstep |
+ *   [3] _stepwidth(0) | [4] the loop index of the last tick |
+ *   [5:32] _footz_ref | [32:59] _lift_height_ref | [59:86] the initial _tx
+ *   (for _Zsc) | [86:374] a ring of QLOCO_NLP_TICK_RING entries of
+ *   (_Rfootx, _Rfooty, _Rfootz, _Lfootx, _Lfooty, _Lfootz): array index k is
+ *   entry k % QLOCO_NLP_TICK_RING.
+ * The ring replaces the reference's arrays of _nsum entries: a tick reads no
+ * further back than round(_tx(_bjx1-1)/_dt) - 2, so the ring has to hold
+ * round(t_max / dt) ticks, that look-back and the forecast slot; init and tick
+ * return QLOCO_ERR_ARG when round(t_max / dt) + 4 exceeds it.  An index past
+ * the last tick + 1 reads as Initialize left the arrays (:496-499), one the
+ * ring no longer holds as NaN (reported as QLOCO_NAN).  The loop index is
+ * expected to advance by one per call, as in the reference. */
+#define QLOCO_NLP_TICK_RING 48
+#define QLOCO_NLP_TICK_STATE 374
+int64_t qloco_nlp_tick_workspace_bytes(int64_t batch);
+/* qloco_nlp_init on nlp_workspace, then the second workspace.  stepheight[B]
+ * NULL: flat ground. */
+int qloco_nlp_tick_init(const qloco_nlp_params *prm, const qloco_nlp_tick_params *tick_prm, int64_t batch,
+                        void *nlp_workspace, void *tick_workspace, const double *steplength,
+                        const double *stepwidth, const double *stepheight, void *stream);
+/* One planner tick of every robot: step_timing_opti_loop followed by
+ * Foot_trajectory_solve_mod2 with the same loop index (NLPRTControlClass.cpp:
+ * 445-459).  Inputs as qloco_nlp_step_timing, plus stop_walking[B] (int32,
+ * NULL = 0).  Outputs: com_traj[B*38], every slot as :1048-1090 fills it
+ * (28..33 NaN on the plan's last step, where the reference reads past the
+ * end); rlfoot_traj[B*18] (R xyz, L xyz, R v, L v, R a, L a; velocity and
+ * acceleration entries the reference does not write on a tick are 0);
+ * right_support[B] (0 left support, 1 right support, 2 double support);
+ * vari_ini[B*4] and the optional sched / step / com / pass_status /
+ * pass_iters of section 14, written by its kernel; status[B] (optional):
+ * section 14's status, or QLOCO_NAN when a value of this section is not
+ * finite.  A robot whose step-timing status is QLOCO_NLP_FINISHED or
+ * QLOCO_BAD_SIZE leaves both records untouched and returns NaN with
+ * right_support 2. */
+int qloco_nlp_tick(const qloco_nlp_params *prm, const qloco_nlp_tick_params *tick_prm, int64_t batch,
+                   void *nlp_workspace, void *tick_workspace, const int32_t *t_int,
+                   const double *estimated_state, const double *rfoot_feedback,
+                   const double *lfoot_feedback, const int32_t *stop_walking, double *com_traj,
+                   double *rlfoot_traj, int32_t *right_support, double *vari_ini, int32_t *sched,
+                   double *step, double *com, int32_t *pass_status, int32_t *pass_iters, int32_t *status,
+                   void *stream);
+/* Form of the new kernel: 1 = one robot per lane (default), 8 = one robot per
+ * 8-lane group with a row of the 7 x 7 system per lane; results do not depend
+ * on it.  Returns the previous value, or QLOCO_ERR_ARG. */
+int qloco_nlp_tick_set_group_width(int gw);
+/* Dense state[B * QLOCO_NLP_TICK_STATE] out of / into the second workspace. */
+int qloco_nlp_tick_get_state(int64_t batch, const void *tick_workspace, double *state, void *stream);
+int qloco_nlp_tick_set_state(int64_t batch, void *tick_workspace, const double *state, void *stream);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,7 @@
  *                                    preamble of compute_grf (:341-380)
  *   A1BasicEKFBatch               <- A1BasicEKF (a1_cpp_open_source/src/A1BasicEKF.h:25-72;
  *                                    GazeboA1ROS.cpp:204-209)
+ *   NLPClassBatch                 <- NLPClass::step_timing_opti_loop + Foot_trajectory_solve_mod2
  *   NLPStepTimingBatch            <- NLPClass::step_timing_opti_loop (mosek_nlp_kmp/src/NLP/
  *                                    NLPClass_sqp.cpp:693-1102; NLPRTControlClass.cpp:445)
  *   Kinematicclass                <- go1_rt_control Kinematicclass
@@ -430,6 +431,55 @@ class NLPStepTimingBatch {
   double *d_in_, *d_out_, *d_rec_;
   int32_t *d_i_, *d_int_;
   std::vector<int32_t> status_;
+};
+
+// ------------------------------------------------------------------------
+// NLPClass up to the class boundary for B robots -> qloco_nlp_tick (section
+// 15): step_timing_opti_loop returns the fully populated 38-vector (slots
+// 28..33 are NaN only on the plan's last step, where the reference reads
+// _footx_ref past its end), Foot_trajectory_solve_mod2 the 18-vector of the
+// same tick, and right_support is the member the reference leaves behind.
+// The device call runs in step_timing_opti_loop with the `stopwalking` it is
+// given; Foot_trajectory_solve_mod2 returns what that call computed and throws
+// when j_index or stopwalking differ from it, or when no tick preceded it
+// (NLPRTControlClass.cpp:445-459 calls the two back to back with the same
+// arguments).  `lamda` is accepted and unused, as in the reference.
+// Zmp_distributor and the _state_generate_interpo packing stay on the host.
+class NLPClassBatch {
+ public:
+  static constexpr int kComTraj = 38, kFootTraj = 18;
+  NLPClassBatch(int batch, double stepwidth, double steplength, double stepheight,
+                const qloco_nlp_params *params = nullptr, const qloco_nlp_tick_params *tick_params = nullptr);
+  // B = 1: the reference's signatures
+  std::array<double, 38> step_timing_opti_loop(int i, const double estimated_state[18],
+                                               const double Rfoot_location_feedback[3],
+                                               const double Lfoot_location_feedback[3], double lamda,
+                                               bool stopwalking);
+  std::array<double, 18> Foot_trajectory_solve_mod2(int j_index, bool stopwalking);
+  // B robots: estimated_state[B*18], feedbacks[B*3] -> com_traj[B*38]; rlfoot_traj[B*18]
+  void step_timing_opti_loop(int i, const double *estimated_state, const double *Rfoot_location_feedback,
+                             const double *Lfoot_location_feedback, double lamda, bool stopwalking,
+                             double *com_traj);
+  void Foot_trajectory_solve_mod2(int j_index, bool stopwalking, double *rlfoot_traj);
+  int right_support = 0;                        // robot 0, after the last tick (:493)
+  std::vector<int32_t> right_support_batch;     // every robot
+  // dense member state: B * QLOCO_NLP_STATE and B * QLOCO_NLP_TICK_STATE doubles
+  void get_state(double *nlp_state, double *tick_state);
+  void set_state(const double *nlp_state, const double *tick_state);
+  const std::vector<int32_t> &status() const { return status_; }
+  qloco_nlp_params params;
+  qloco_nlp_tick_params tick_params;
+  int batch() const { return batch_; }
+
+ private:
+  int batch_, last_i_ = 0;
+  bool last_stop_ = false, have_tick_ = false;
+  DeviceArena arena_;
+  void *d_ws_, *d_tws_;
+  double *d_in_, *d_out_, *d_rec_, *d_trec_;
+  int32_t *d_i_, *d_int_;
+  std::vector<int32_t> status_;
+  std::vector<double> foot_;
 };
 
 // ------------------------------------------------------------------------

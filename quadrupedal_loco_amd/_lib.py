@@ -87,6 +87,11 @@ class NlpParams(C.Structure):
         "lamda_comx", "lamda_comvx", "lamda_comy", "lamda_comvy")] + [("reserved", C.c_double * 2)]
 
 
+class NlpTickParams(C.Structure):
+    """Mirror of `qloco_nlp_tick_params`."""
+    _fields_ = [("lift_height", C.c_double), ("hcom", C.c_double), ("reserved", C.c_double * 6)]
+
+
 vp = C.c_void_p
 i64 = C.c_int64
 i32 = C.c_int32
@@ -161,6 +166,13 @@ SIGNATURES = {
     "qloco_nlp_get_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_nlp_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_nlp_set_group_width": (C.c_int, [C.c_int]),
+    "qloco_nlp_tick_params_default": (None, [C.POINTER(NlpTickParams)]),
+    "qloco_nlp_tick_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_nlp_tick_init": (C.c_int, [C.POINTER(NlpParams), C.POINTER(NlpTickParams), i64] + [vp] * 6),
+    "qloco_nlp_tick": (C.c_int, [C.POINTER(NlpParams), C.POINTER(NlpTickParams), i64] + [vp] * 18),
+    "qloco_nlp_tick_set_group_width": (C.c_int, [C.c_int]),
+    "qloco_nlp_tick_get_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_tick_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),
     "qloco_mgpu_gather_rows": (C.c_int, [i64, i32, i32, vp]),
     "qloco_mgpu_reorder": (C.c_int, [i64, i32, i32, i32, vp, vp, vp, vp, vp]),

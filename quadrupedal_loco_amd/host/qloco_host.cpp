@@ -979,6 +979,128 @@ void NLPStepTimingBatch::set_state(const double *state) {
 }
 
 // ------------------------------------------------------------------------
+// NLPClassBatch -> qloco_nlp_tick
+namespace {
+// device input block, per robot: est[6] | rfoot[2] | lfoot[2] | stepheight[1];
+// output block: com_traj[38] | rlfoot[18] | vari[4]; int block: t_int | stop |
+// right_support | status
+constexpr size_t kTI_N = 11, kTO_CT = 0, kTO_RL = 38, kTO_VARI = 56, kTO_N = 60;
+}  // namespace
+
+NLPClassBatch::NLPClassBatch(int batch, double stepwidth, double steplength, double stepheight,
+                             const qloco_nlp_params *p, const qloco_nlp_tick_params *tp)
+    : batch_(positive_batch(batch, "NLPClassBatch")) {
+  if (p) params = *p;
+  else qloco_nlp_params_default(&params);
+  if (tp) tick_params = *tp;
+  else qloco_nlp_tick_params_default(&tick_params);
+  const size_t B = batch;
+  const int64_t ws = qloco_nlp_workspace_bytes(batch), tws = qloco_nlp_tick_workspace_bytes(batch);
+  if (ws < 0 || tws < 0) throw Error("qloco_nlp_tick_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_tws_ = arena_.alloc((size_t)tws);
+  d_in_ = dalloc<double>(arena_, B * kTI_N);
+  d_out_ = dalloc<double>(arena_, B * kTO_N);
+  d_rec_ = dalloc<double>(arena_, B * QLOCO_NLP_STATE);
+  d_trec_ = dalloc<double>(arena_, B * QLOCO_NLP_TICK_STATE);
+  d_i_ = dalloc<int32_t>(arena_, 2 * B);
+  d_int_ = dalloc<int32_t>(arena_, 2 * B);
+  status_.assign(B, QLOCO_OK);
+  right_support_batch.assign(B, 0);
+  foot_.assign(B * kFootTraj, 0.0);
+  std::vector<double> in(3 * B);
+  for (size_t b = 0; b < B; ++b) {
+    in[b] = steplength;
+    in[B + b] = stepwidth;
+    in[2 * B + b] = stepheight;
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  abi_ok(qloco_nlp_tick_init(&params, &tick_params, batch_, d_ws_, d_tws_, d_in_, d_in_ + B, d_in_ + 2 * B,
+                             arena_.stream()),
+         "qloco_nlp_tick_init");
+  arena_.sync();
+}
+
+void NLPClassBatch::step_timing_opti_loop(int i, const double *est, const double *rfoot, const double *lfoot,
+                                          double /*lamda*/, bool stopwalking, double *com_traj) {
+  if (!est || !rfoot || !lfoot || !com_traj)
+    throw Error("NLPClassBatch::step_timing_opti_loop: null argument", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  std::vector<double> in(B * 10);
+  std::vector<int32_t> ti(2 * B, i);
+  for (size_t b = 0; b < B; ++b) {
+    for (int k = 0; k < 6; ++k) in[6 * b + k] = est[18 * b + k];
+    for (int k = 0; k < 2; ++k) {
+      in[6 * B + 2 * b + k] = rfoot[3 * b + k];
+      in[8 * B + 2 * b + k] = lfoot[3 * b + k];
+    }
+    ti[B + b] = stopwalking ? 1 : 0;
+  }
+  arena_.upload(d_in_, in.data(), sizeof(double) * in.size());
+  arena_.upload(d_i_, ti.data(), sizeof(int32_t) * ti.size());
+  abi_ok(qloco_nlp_tick(&params, &tick_params, batch_, d_ws_, d_tws_, d_i_, d_in_, d_in_ + 6 * B, d_in_ + 8 * B,
+                        d_i_ + B, d_out_ + kTO_CT * B, d_out_ + kTO_RL * B, d_int_, d_out_ + kTO_VARI * B, nullptr,
+                        nullptr, nullptr, nullptr, nullptr, d_int_ + B, arena_.stream()),
+         "qloco_nlp_tick");
+  std::vector<int32_t> ints(2 * B);
+  arena_.download(com_traj, d_out_ + kTO_CT * B, sizeof(double) * B * kComTraj);
+  arena_.download(foot_.data(), d_out_ + kTO_RL * B, sizeof(double) * B * kFootTraj);
+  arena_.download(ints.data(), d_int_, sizeof(int32_t) * ints.size());
+  arena_.sync();
+  for (size_t b = 0; b < B; ++b) {
+    right_support_batch[b] = ints[b];
+    status_[b] = ints[B + b];
+  }
+  right_support = right_support_batch[0];
+  last_i_ = i;
+  last_stop_ = stopwalking;
+  have_tick_ = true;
+}
+
+std::array<double, 38> NLPClassBatch::step_timing_opti_loop(int i, const double estimated_state[18],
+                                                            const double Rfoot[3], const double Lfoot[3],
+                                                            double lamda, bool stopwalking) {
+  if (batch_ != 1) throw Error("NLPClassBatch: the single-robot call needs batch 1", QLOCO_ERR_ARG);
+  std::array<double, 38> r;
+  step_timing_opti_loop(i, estimated_state, Rfoot, Lfoot, lamda, stopwalking, r.data());
+  return r;
+}
+
+void NLPClassBatch::Foot_trajectory_solve_mod2(int j_index, bool stopwalking, double *rlfoot_traj) {
+  if (!rlfoot_traj) throw Error("NLPClassBatch::Foot_trajectory_solve_mod2: null output", QLOCO_ERR_ARG);
+  if (!have_tick_ || j_index != last_i_ || stopwalking != last_stop_)
+    throw Error("NLPClassBatch::Foot_trajectory_solve_mod2: call step_timing_opti_loop with the same index and "
+                "stopwalking first",
+                QLOCO_ERR_ARG);
+  std::copy(foot_.begin(), foot_.end(), rlfoot_traj);
+}
+
+std::array<double, 18> NLPClassBatch::Foot_trajectory_solve_mod2(int j_index, bool stopwalking) {
+  if (batch_ != 1) throw Error("NLPClassBatch: the single-robot call needs batch 1", QLOCO_ERR_ARG);
+  std::array<double, 18> r;
+  Foot_trajectory_solve_mod2(j_index, stopwalking, r.data());
+  return r;
+}
+
+void NLPClassBatch::get_state(double *nlp_state, double *tick_state) {
+  if (!nlp_state || !tick_state) throw Error("NLPClassBatch::get_state: null output", QLOCO_ERR_ARG);
+  abi_ok(qloco_nlp_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_get_state");
+  abi_ok(qloco_nlp_tick_get_state(batch_, d_tws_, d_trec_, arena_.stream()), "qloco_nlp_tick_get_state");
+  arena_.download(nlp_state, d_rec_, sizeof(double) * (size_t)batch_ * QLOCO_NLP_STATE);
+  arena_.download(tick_state, d_trec_, sizeof(double) * (size_t)batch_ * QLOCO_NLP_TICK_STATE);
+  arena_.sync();
+}
+
+void NLPClassBatch::set_state(const double *nlp_state, const double *tick_state) {
+  if (!nlp_state || !tick_state) throw Error("NLPClassBatch::set_state: null input", QLOCO_ERR_ARG);
+  arena_.upload(d_rec_, nlp_state, sizeof(double) * (size_t)batch_ * QLOCO_NLP_STATE);
+  arena_.upload(d_trec_, tick_state, sizeof(double) * (size_t)batch_ * QLOCO_NLP_TICK_STATE);
+  abi_ok(qloco_nlp_set_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_set_state");
+  abi_ok(qloco_nlp_tick_set_state(batch_, d_tws_, d_trec_, arena_.stream()), "qloco_nlp_tick_set_state");
+  arena_.sync();
+}
+
+// ------------------------------------------------------------------------
 // Kinematicclass -> qloco_leg_fk / qloco_leg_ik
 Kinematicclass::Kinematicclass(int max_legs) : cap_(0) {
   if (max_legs < 1) throw Error("Kinematicclass: max_legs < 1", QLOCO_ERR_ARG);

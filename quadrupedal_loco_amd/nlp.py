@@ -14,13 +14,16 @@ views of it in the layout `qloco_support_phase` takes, so
     out = planner.tick(t_int, est, rfoot, lfoot)
     rt.support_phase(planner.ts, planner.tx, t_int, t_end)
 
-chains on one stream with no copy.  Not computed: CoM_height_solve (and with
-it _comz, ZMP, DCM), the foot trajectories and KMP.
+chains on one stream with no copy.  `StepTimingPlanner` does not compute
+CoM_height_solve (and with it _comz, ZMP, DCM) or the foot trajectories;
+`PlannerTick` (`qloco_nlp_tick`, csrc/qloco_nlp_tick.hip) runs the same SQP
+kernel and adds them: the full 38-vector of step_timing_opti_loop and the
+18-vector and support flag of Foot_trajectory_solve_mod2.  KMP is not computed.
 """
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import NlpParams, check, lib, ptr
+from ._lib import NlpParams, NlpTickParams, check, lib, ptr
 from .a1est import _dev
 
 NS = 27               # QLOCO_NLP_STEPS
@@ -132,10 +135,121 @@ class StepTimingPlanner:
               "qloco_nlp_set_state")
 
 
+TICK_STATE = 374      # QLOCO_NLP_TICK_STATE
+TICK_RING = 48        # QLOCO_NLP_TICK_RING
+TICK_STATE_FIELDS = dict(  # slices of the dense record of the second workspace
+    bjx1=(0, 1), ry=(1, 2), t_end=(2, 3), sw0=(3, 4), last=(4, 5), footz_ref=(5, 32), lift=(32, 59),
+    tx0=(59, 86), ring=(86, 374))
+
+
+def default_tick_params(**overrides):
+    """_lift_height (NLPRTControlClass.cpp:48) and _hcom (NLPClass_sqp.cpp:212)."""
+    p = NlpTickParams()
+    lib().qloco_nlp_tick_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k == "reserved" or not hasattr(p, k):
+            raise ValueError("unknown parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+@dataclass
+class PlannerTickResult:
+    com_traj: object       # (B, 38): step_timing_opti_loop's return value, every slot
+    rlfoot_traj: object    # (B, 18): Foot_trajectory_solve_mod2's return value
+    right_support: object  # (B,) int32: 0 left support, 1 right support, 2 double support
+    status: object         # (B,) int32
+    step_timing: object    # StepTimingResult of the same tick (its status is `status`)
+
+
+class PlannerTick(StepTimingPlanner):
+    """Batched drop-in for one NLPClass tick up to the class boundary:
+    step_timing_opti_loop followed by Foot_trajectory_solve_mod2.  The SQP's
+    record (`get_state`) and kernel are StepTimingPlanner's; the members it
+    lacks live in a second workspace (`get_tick_state`)."""
+
+    def __init__(self, batch, device, params=None, tick_params=None, steplength=0.075, stepwidth=None,
+                 stepheight=None, **overrides):
+        import torch
+        self.tick_params = tick_params if tick_params is not None else default_tick_params()
+        nbytes = lib().qloco_nlp_tick_workspace_bytes(int(batch))
+        if nbytes <= 0:
+            raise ValueError("qloco_nlp_tick_workspace_bytes(%d) = %d" % (batch, nbytes))
+        self.tick_workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=torch.device(device))
+        self._stepheight = stepheight
+        super().__init__(batch, device, params=params, steplength=steplength, stepwidth=stepwidth, **overrides)
+
+    def init(self, steplength, stepwidth, stepheight=None, stream=None):
+        """FootStepInputs + Initialize of both records: scalars or per-robot
+        (B,) values; stepheight None is flat ground."""
+        sl = self._per_robot(steplength, "steplength")
+        sw = self._per_robot(stepwidth, "stepwidth")
+        if stepheight is None:
+            stepheight = self._stepheight
+        sh = None if stepheight is None else self._per_robot(stepheight, "stepheight")
+        check(lib().qloco_nlp_tick_init(C.byref(self.params), C.byref(self.tick_params), self.batch,
+                                        ptr(self.workspace), ptr(self.tick_workspace), ptr(sl), ptr(sw),
+                                        None if sh is None else ptr(sh), self._stream(stream)),
+              "qloco_nlp_tick_init")
+
+    def step_timing_tick(self, t_int, estimated_state, rfoot_feedback, lfoot_feedback, out=None, stream=None):
+        """The SQP alone (StepTimingPlanner.tick): the second record is not advanced."""
+        return super().tick(t_int, estimated_state, rfoot_feedback, lfoot_feedback, out=out, stream=stream)
+
+    def tick(self, t_int, estimated_state, rfoot_feedback, lfoot_feedback, stop_walking=None, out=None,
+             stream=None):
+        """One planner tick: the inputs of StepTimingPlanner.tick and an
+        optional stop_walking (B,) int32.  out: a PlannerTickResult of an
+        earlier call to write into."""
+        import torch
+        B = self.batch
+        _dev(t_int, "i32", (B,), "t_int")
+        _dev(estimated_state, "f64", (B, 6), "estimated_state")
+        _dev(rfoot_feedback, "f64", (B, 2), "rfoot_feedback")
+        _dev(lfoot_feedback, "f64", (B, 2), "lfoot_feedback")
+        if stop_walking is not None:
+            _dev(stop_walking, "i32", (B,), "stop_walking")
+        if out is None:
+            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)
+            st = StepTimingResult(self._f64(B, 4), i32(B, 4), self._f64(B, 3), self._f64(B, 18), i32(B, 3),
+                                  i32(B, 3), i32(B))
+            out = PlannerTickResult(self._f64(B, 38), self._f64(B, 18), i32(B), st.status, st)
+        st = out.step_timing
+        check(lib().qloco_nlp_tick(
+            C.byref(self.params), C.byref(self.tick_params), B, ptr(self.workspace), ptr(self.tick_workspace),
+            ptr(t_int), ptr(estimated_state), ptr(rfoot_feedback), ptr(lfoot_feedback),
+            None if stop_walking is None else ptr(stop_walking), ptr(out.com_traj), ptr(out.rlfoot_traj),
+            ptr(out.right_support), ptr(st.vari_ini), ptr(st.sched), ptr(st.step), ptr(st.com),
+            ptr(st.pass_status), ptr(st.pass_iters), ptr(st.status), self._stream(stream)), "qloco_nlp_tick")
+        return out
+
+    def get_tick_state(self, stream=None):
+        """Dense (B, 374) second record per robot (TICK_STATE_FIELDS)."""
+        s = self._f64(self.batch, TICK_STATE)
+        check(lib().qloco_nlp_tick_get_state(self.batch, ptr(self.tick_workspace), ptr(s), self._stream(stream)),
+              "qloco_nlp_tick_get_state")
+        return s
+
+    def set_tick_state(self, state, stream=None):
+        _dev(state, "f64", (self.batch, TICK_STATE), "state")
+        check(lib().qloco_nlp_tick_set_state(self.batch, ptr(self.tick_workspace), ptr(state), self._stream(stream)),
+              "qloco_nlp_tick_set_state")
+
+
 def set_group_width(gw):
     """Lanes per robot of the tick kernel (4, 8 or 16); returns the previous
     width.  A throughput knob: results do not depend on it."""
     r = lib().qloco_nlp_set_group_width(int(gw))
     if r == 100:
         raise ValueError("group width must be 4, 8 or 16")
+    return r
+
+
+def set_tick_group_width(gw):
+    """Form of the second kernel of PlannerTick.tick: 1 (one robot per lane) or
+    8 (one robot per 8-lane group); returns the previous value.  A throughput
+    knob: results do not depend on it."""
+    r = lib().qloco_nlp_tick_set_group_width(int(gw))
+    if r == 100:
+        raise ValueError("group width must be 1 or 8")
     return r
