@@ -893,6 +893,111 @@ int qloco_nlp_tick_set_group_width(int gw);
 int qloco_nlp_tick_get_state(int64_t batch, const void *tick_workspace, double *state, void *stream);
 int qloco_nlp_tick_set_state(int64_t batch, void *tick_workspace, const double *state, void *stream);
 
+/* ====================================================================== */
+/* 16. go1 servo tick, batched (fp64): joint state, IMU quaternion and the */
+/*    /MPC/Gait row in, joint commands, torques and /control2rtmpc/state   */
+/*    out.  Replaces one iteration of the sim servo loop, go1_rt_control/  */
+/*    src/servo_control/servo.cpp:675-1330, and the go1_gait_data row of   */
+/*    :1333-1433: quat_to_euler + Forward_kinematics_g x 4 (:690-741), the */
+/*    measured foot velocity (:749-755), the state row (:758-762), the     */
+/*    stand-up branch (:769-809) or the gait branch (:889-1051: counters,  */
+/*    15 Butterworth filters, per-mode targets, Inverse_kinematics_g x 4)  */
+/*    followed by section 7's force block (:1052-1243), the joint commands */
+/*    (:1265-1296) and the end-of-loop updates (:1318-1330).  Not          */
+/*    computed: root_rot_mat / root_rot_mat_z (never read), the callbacks  */
+/*    and publishers, the hardware loop (torque_mode.cpp).                 */
+/* ====================================================================== */
+/* One second-order Butterworth low-pass (Filter/butterworthLPF.cpp:83-120):
+ * init()'s coefficients, computed on the host with its expressions and its
+ * 3.14159265359; the kernel never calls tan. */
+typedef struct qloco_butter_coef {
+  double b0, b1, b2, a1, a2, a;
+} qloco_butter_coef;
+/* The 15 live filters in the loop's order (index: reference filter, gait slot):
+ *   0-2  LPF1-3   com_des       slots 0-2      3 Hz
+ *   3-5  LPF7-9   rfoot_des     slots 9-11     3 Hz
+ *   6-8  LPF10-12 lfoot_des     slots 6-8      3, 3, 10 Hz (:593, kept)
+ *   9-11 LPF13-15 coma_des      slots 39-41    10 Hz
+ *  12-14 LPF16-18 thetaacc_des  slots 73-75    10 Hz */
+#define QLOCO_GO1_SERVO_FILTERS 15
+typedef struct qloco_go1_servo_params {
+  double rt_frequency;    /* 1000     servo.cpp:633 (time_programming = 1 / it) */
+  double stand_duration;  /* 5        :639 */
+  double dtx;             /* 0.005    gait::t_program_cyclic (:567) */
+  double dt_mpc_slow;     /* 0.025    n_t_int = round(dt_mpc_slow / dtx) (:568) */
+  double t_period;        /* 0.7      n_period = round(t_period / dtx) (:616) */
+  double t_walk_start;    /* 0.6      the gate of :933 */
+  double pi;              /* 3.141526 gait::pi (sic), mode 103's pitch (:998) */
+  double half_hip_width;  /* 0.12675  RobotParaClass_HALF_HIP_WIDTH */
+  double z_c;             /* 0.309458 gait::Z_c: com_des(2) of paramInit (:450) */
+  double target_pos[12];  /* :767 */
+  qloco_butter_coef filter[QLOCO_GO1_SERVO_FILTERS];
+  qloco_force_params force;  /* the Dynamiccclass constants of section 3 */
+  double reserved[8];        /* room for the hardware loop's constants */
+} qloco_go1_servo_params;
+void qloco_go1_servo_params_default(qloco_go1_servo_params *p);
+
+/* Per-robot state, as get_state / set_state move it: a dense record of
+ * QLOCO_GO1_SERVO_STATE doubles (integers and flags as doubles):
+ *   [0:75]    the 15 filters, 5 each: y_p, y_pp, x_p, x_pp, i (calls, <= 3)
+ *   [75:87]   angle_des (FR, FL, RR, RL)   [87:99]   FR..RL_foot_Homing
+ *   [99:102]  body_p_Homing                [102:105] body_p_des
+ *   [105:108] body_r_des                   [108:120] FR..RL_foot_des
+ *   [120:132] foot_relative_des_old        [132:144] foot_relative_mea_old
+ *   [144:147] com_des_pre                  [147:159] v_relative
+ *   [159:171] v_est_relative               [171]     count_in_rt_loop
+ *   [172:176] FR..RL_swing                 [176:188] F_leg_ref (3 x 4 col-major)
+ *   [188:200] grf_opt                      [200:212] Legs_torque
+ *   [212:230] com_des, rfoot_des, lfoot_des, coma_des, thetaacc_des, comv_des
+ *   [230]     state_feedback(0) = t_int    [231:237] Force_L_R
+ *   [237:243] F_sum                        [243:279] FR..RL_Jaco (col-major)
+ *   [279]     qp_solution  [280] EiQuadProg status  [281:288] 0
+ * The force QP's grouping workspace is a cache, not state: results are
+ * bit-identical with or without it, and set_state leaves it alone. */
+#define QLOCO_GO1_SERVO_STATE 288
+#define QLOCO_GO1_GAIT_DATA_LEN 100
+/* Optional device outputs of a tick (any may be NULL), [B * n] each: the
+ * reference's members of the same names after the tick. */
+typedef struct qloco_go1_servo_diag {
+  double *body_r_est;   /* 3 */
+  double *foot_rel_mea; /* 12 */
+  double *v_est_rel;    /* 12 */
+  double *Jaco_est;     /* 36 */
+  double *com_des, *rfoot_des, *lfoot_des, *coma_des, *thetaacc_des, *comv_des; /* 3 each */
+  double *body_p_des, *body_r_des; /* 3 each */
+  double *foot_des;     /* 12 */
+  double *angle_des;    /* 12 */
+  double *Jaco;         /* 36 */
+  int32_t *ik_updates;  /* 4: Newton steps applied per leg (0 while standing up) */
+  double *F_sum, *Force_L_R; /* 6 each */
+  int32_t *swing;       /* 4 */
+  int32_t *qp_solution, *status; /* 1 each */
+} qloco_go1_servo_diag;
+/* Bytes of the device workspace of B robots (-1 for batch <= 0). */
+int64_t qloco_go1_servo_workspace_bytes(int64_t batch);
+/* paramInit (:300-470) and the member setup of main (:556-616) for B robots. */
+int qloco_go1_servo_init(const qloco_go1_servo_params *prm, int64_t batch, void *workspace,
+                         void *stream);
+/* One loop iteration of B robots started together.  n_count: the node's loop
+ * counter (host; the caller increments it), so the branch of :769 is uniform
+ * over the batch and count_in_rt_ros = n_count + 1; count_in_rt_loop is
+ * per-robot state.  Device inputs: q_mea[B*12] (lowState.motorState[j].q),
+ * quat[B*4] (w, x, y, z), gait_msg[B*100] (the latest /MPC/Gait row),
+ * gait_mode[B] (int32), y_offset[B].  Device outputs: q_cmd[B*12],
+ * ctrl_msg[B*25] (the row published at :762, i.e. [0] = the previous tick's
+ * t_int, the rest 0), tau[B*12] (Legs_torque), grf_opt[B*12]; optional
+ * diag and gait_data[B*100] ([0:90] as :1335-1433 writes them, the rest 0).
+ * While standing up the force QP is not launched: tau, grf_opt and the swing
+ * flags keep their values. */
+int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t batch, void *workspace,
+                         int64_t n_count, const double *q_mea, const double *quat,
+                         const double *gait_msg, const int32_t *gait_mode, const double *y_offset,
+                         double *q_cmd, double *ctrl_msg, double *tau, double *grf_opt,
+                         const qloco_go1_servo_diag *diag, double *gait_data, void *stream);
+/* Dense state[B * QLOCO_GO1_SERVO_STATE] out of / into the workspace. */
+int qloco_go1_servo_get_state(int64_t batch, const void *workspace, double *state, void *stream);
+int qloco_go1_servo_set_state(int64_t batch, void *workspace, const double *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@
  *                                    preamble of compute_grf (:341-380)
  *   A1BasicEKFBatch               <- A1BasicEKF (a1_cpp_open_source/src/A1BasicEKF.h:25-72;
  *                                    GazeboA1ROS.cpp:204-209)
+ *   Go1ServoBatch                 <- one iteration of the go1 sim servo loop (go1_rt_control/
+ *                                    src/servo_control/servo.cpp:675-1330)
  *   NLPClassBatch                 <- NLPClass::step_timing_opti_loop + Foot_trajectory_solve_mod2
  *   NLPStepTimingBatch            <- NLPClass::step_timing_opti_loop (mosek_nlp_kmp/src/NLP/
  *                                    NLPClass_sqp.cpp:693-1102; NLPRTControlClass.cpp:445)
@@ -574,6 +576,41 @@ class ServoForceBlock {
   void *d_ws_;
   double *d_in_, *d_out_;
   int32_t *d_iin_, *d_iout_;
+};
+
+// ------------------------------------------------------------------------
+// One iteration of the go1 sim servo loop (servo.cpp:675-1330) for B robots
+// started together (batch 1: the drop-in case).  The callbacks fill the three
+// inputs, tick() runs the loop body on the device (qloco.h section 16) and
+// leaves the reference's members, by their names, in host arrays (robot b's
+// values at b * n); the publishers stay with the caller.  n_count is the
+// node's loop counter, incremented by tick().
+class Go1ServoBatch {
+ public:
+  explicit Go1ServoBatch(int batch = 1, const qloco_go1_servo_params *params = nullptr);
+  // q_mea[B*12] (lowState.motorState[j].q), quat[B*4] (w, x, y, z), slow_mpc_gait[B*100]
+  // (the latest /MPC/Gait row), gait_mode[B], y_offset[B]
+  void tick(const double *q_mea, const double *quat, const double *slow_mpc_gait,
+            const int32_t *gait_mode, const double *y_offset);
+  std::vector<double> q_cmd;           // lowCmd.motorCmd[j].q, B*12
+  std::vector<double> state_to_MPC;    // the /control2rtmpc/state row published at :762, B*25
+  std::vector<double> state_feedback;  // the member after the tick ([0] = t_int), B*25
+  std::vector<double> Legs_torque, grf_opt;                                    // B*12
+  std::vector<double> FR_angle_des, FL_angle_des, RR_angle_des, RL_angle_des;  // 12-vectors: B*3
+  std::vector<double> joint2simulation;                                        // go1_gait_data, B*100
+  int n_count = 0;
+  // dense member state: B * QLOCO_GO1_SERVO_STATE doubles
+  void get_state(double *state);
+  void set_state(const double *state);
+  qloco_go1_servo_params params;
+  int batch() const { return batch_; }
+
+ private:
+  int batch_;
+  DeviceArena arena_;
+  void *d_ws_;
+  double *d_in_, *d_out_, *d_rec_;
+  int32_t *d_mode_;
 };
 
 }  // namespace qloco

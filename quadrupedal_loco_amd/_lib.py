@@ -92,6 +92,33 @@ class NlpTickParams(C.Structure):
     _fields_ = [("lift_height", C.c_double), ("hcom", C.c_double), ("reserved", C.c_double * 6)]
 
 
+class ButterCoef(C.Structure):
+    """Mirror of `qloco_butter_coef`."""
+    _fields_ = [(k, C.c_double) for k in ("b0", "b1", "b2", "a1", "a2", "a")]
+
+
+class Go1ServoParams(C.Structure):
+    """Mirror of `qloco_go1_servo_params`."""
+    _fields_ = [(k, C.c_double) for k in (
+        "rt_frequency", "stand_duration", "dtx", "dt_mpc_slow", "t_period", "t_walk_start", "pi",
+        "half_hip_width", "z_c")] + [("target_pos", C.c_double * 12), ("filter", ButterCoef * 15),
+                                     ("force", ForceParams), ("reserved", C.c_double * 8)]
+
+
+GO1_SERVO_DIAG = (("body_r_est", 3, "f8"), ("foot_rel_mea", 12, "f8"), ("v_est_rel", 12, "f8"),
+                  ("Jaco_est", 36, "f8"), ("com_des", 3, "f8"), ("rfoot_des", 3, "f8"),
+                  ("lfoot_des", 3, "f8"), ("coma_des", 3, "f8"), ("thetaacc_des", 3, "f8"),
+                  ("comv_des", 3, "f8"), ("body_p_des", 3, "f8"), ("body_r_des", 3, "f8"),
+                  ("foot_des", 12, "f8"), ("angle_des", 12, "f8"), ("Jaco", 36, "f8"),
+                  ("ik_updates", 4, "i4"), ("F_sum", 6, "f8"), ("Force_L_R", 6, "f8"),
+                  ("swing", 4, "i4"), ("qp_solution", 1, "i4"), ("status", 1, "i4"))
+
+
+class Go1ServoDiag(C.Structure):
+    """Mirror of `qloco_go1_servo_diag`: one device pointer per member."""
+    _fields_ = [(k, C.c_void_p) for k, _, _ in GO1_SERVO_DIAG]
+
+
 vp = C.c_void_p
 i64 = C.c_int64
 i32 = C.c_int32
@@ -173,6 +200,13 @@ SIGNATURES = {
     "qloco_nlp_tick_set_group_width": (C.c_int, [C.c_int]),
     "qloco_nlp_tick_get_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_nlp_tick_set_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_go1_servo_params_default": (None, [C.POINTER(Go1ServoParams)]),
+    "qloco_go1_servo_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_go1_servo_init": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, vp]),
+    "qloco_go1_servo_tick": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, i64] + [vp] * 9 +
+                             [C.POINTER(Go1ServoDiag), vp, vp]),
+    "qloco_go1_servo_get_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_go1_servo_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),
     "qloco_mgpu_gather_rows": (C.c_int, [i64, i32, i32, vp]),
     "qloco_mgpu_reorder": (C.c_int, [i64, i32, i32, i32, vp, vp, vp, vp, vp]),

@@ -1327,4 +1327,89 @@ void ServoForceBlock::step(const double *coma_des, const double *com_des, const 
   arena_.sync();
 }
 
+// ------------------------------------------------------------------------
+// Go1ServoBatch
+namespace {
+// d_in_: q_mea 12 | quat 4 | gait 100 | y_offset 1; d_out_: q_cmd 12 | ctrl 25 | tau 12 | grf 12 | data 100
+constexpr size_t kGI_Q = 0, kGI_QUAT = 12, kGI_GAIT = 16, kGI_Y = 116, kGI_N = 117;
+constexpr size_t kGO_Q = 0, kGO_CTRL = 12, kGO_TAU = 37, kGO_GRF = 49, kGO_DATA = 61, kGO_N = 161;
+}  // namespace
+
+Go1ServoBatch::Go1ServoBatch(int batch, const qloco_go1_servo_params *p)
+    : batch_(positive_batch(batch, "Go1ServoBatch")) {
+  if (p) params = *p;
+  else qloco_go1_servo_params_default(&params);
+  const size_t B = batch;
+  const int64_t ws = qloco_go1_servo_workspace_bytes(batch);
+  if (ws < 0) throw Error("qloco_go1_servo_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_in_ = dalloc<double>(arena_, B * kGI_N);
+  d_out_ = dalloc<double>(arena_, B * kGO_N);
+  d_rec_ = dalloc<double>(arena_, B * QLOCO_GO1_SERVO_STATE);
+  d_mode_ = dalloc<int32_t>(arena_, B);
+  q_cmd.assign(B * 12, 0.0);
+  state_to_MPC.assign(B * QLOCO_CTRL_MSG_LEN, 0.0);
+  state_feedback.assign(B * QLOCO_CTRL_MSG_LEN, 0.0);
+  Legs_torque.assign(B * 12, 0.0);
+  grf_opt.assign(B * 12, 0.0);
+  FR_angle_des.assign(B * 3, 0.0);
+  FL_angle_des.assign(B * 3, 0.0);
+  RR_angle_des.assign(B * 3, 0.0);
+  RL_angle_des.assign(B * 3, 0.0);
+  joint2simulation.assign(B * QLOCO_GO1_GAIT_DATA_LEN, 0.0);
+  abi_ok(qloco_go1_servo_init(&params, batch_, d_ws_, arena_.stream()), "qloco_go1_servo_init");
+  arena_.sync();
+}
+
+void Go1ServoBatch::tick(const double *q_mea, const double *quat, const double *gait,
+                         const int32_t *gait_mode, const double *y_offset) {
+  if (!q_mea || !quat || !gait || !gait_mode || !y_offset)
+    throw Error("Go1ServoBatch::tick: null argument", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  arena_.upload(d_in_ + kGI_Q * B, q_mea, sizeof(double) * 12 * B);
+  arena_.upload(d_in_ + kGI_QUAT * B, quat, sizeof(double) * 4 * B);
+  arena_.upload(d_in_ + kGI_GAIT * B, gait, sizeof(double) * QLOCO_GAIT_MSG_LEN * B);
+  arena_.upload(d_in_ + kGI_Y * B, y_offset, sizeof(double) * B);
+  arena_.upload(d_mode_, gait_mode, sizeof(int32_t) * B);
+  abi_ok(qloco_go1_servo_tick(&params, batch_, d_ws_, n_count, d_in_ + kGI_Q * B,
+                              d_in_ + kGI_QUAT * B, d_in_ + kGI_GAIT * B, d_mode_,
+                              d_in_ + kGI_Y * B, d_out_ + kGO_Q * B, d_out_ + kGO_CTRL * B,
+                              d_out_ + kGO_TAU * B, d_out_ + kGO_GRF * B, nullptr,
+                              d_out_ + kGO_DATA * B, arena_.stream()),
+         "qloco_go1_servo_tick");
+  arena_.download(q_cmd.data(), d_out_ + kGO_Q * B, sizeof(double) * 12 * B);
+  arena_.download(state_to_MPC.data(), d_out_ + kGO_CTRL * B, sizeof(double) * QLOCO_CTRL_MSG_LEN * B);
+  arena_.download(Legs_torque.data(), d_out_ + kGO_TAU * B, sizeof(double) * 12 * B);
+  arena_.download(grf_opt.data(), d_out_ + kGO_GRF * B, sizeof(double) * 12 * B);
+  arena_.download(joint2simulation.data(), d_out_ + kGO_DATA * B,
+                  sizeof(double) * QLOCO_GO1_GAIT_DATA_LEN * B);
+  std::vector<double> rec(B * QLOCO_GO1_SERVO_STATE);
+  get_state(rec.data());  // syncs
+  for (size_t b = 0; b < B; ++b) {
+    const double *r = rec.data() + b * QLOCO_GO1_SERVO_STATE;
+    for (int k = 0; k < 3; ++k) {
+      FR_angle_des[3 * b + k] = r[75 + k];
+      FL_angle_des[3 * b + k] = r[78 + k];
+      RR_angle_des[3 * b + k] = r[81 + k];
+      RL_angle_des[3 * b + k] = r[84 + k];
+    }
+    state_feedback[QLOCO_CTRL_MSG_LEN * b] = r[230];
+  }
+  ++n_count;
+}
+
+void Go1ServoBatch::get_state(double *state) {
+  if (!state) throw Error("Go1ServoBatch::get_state: null argument", QLOCO_ERR_ARG);
+  abi_ok(qloco_go1_servo_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_go1_servo_get_state");
+  arena_.download(state, d_rec_, sizeof(double) * (size_t)batch_ * QLOCO_GO1_SERVO_STATE);
+  arena_.sync();
+}
+
+void Go1ServoBatch::set_state(const double *state) {
+  if (!state) throw Error("Go1ServoBatch::set_state: null argument", QLOCO_ERR_ARG);
+  arena_.upload(d_rec_, state, sizeof(double) * (size_t)batch_ * QLOCO_GO1_SERVO_STATE);
+  abi_ok(qloco_go1_servo_set_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_go1_servo_set_state");
+  arena_.sync();
+}
+
 }  // namespace qloco
