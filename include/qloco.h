@@ -998,6 +998,102 @@ int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t batch, void 
 int qloco_go1_servo_get_state(int64_t batch, const void *workspace, double *state, void *stream);
 int qloco_go1_servo_set_state(int64_t batch, void *workspace, const double *state, void *stream);
 
+/* ====================================================================== */
+/* 17. slow planner node tick, batched (fp64): /rt2nrt/state in, the       */
+/*    /MPC/Gait row out.  Replaces one iteration of the node loop,         */
+/*    unitree_ros/mosek_nlp_kmp/src/gait_nlp_kmp.cpp:40-60, 101-158, and   */
+/*    NLPRTControlClass::WalkingReactStepping / rt_nlp_gait                */
+/*    (NLPRTControl/NLPRTControlClass.cpp:191-396, :436-596) around        */
+/*    section 15's tick, which is launched unchanged: the start latch and  */
+/*    loop counter, the branch (not started, squat, walking, over time,    */
+/*    stopped), X_CoM_position_squat (NLPClass_sqp.cpp:2958-3015),         */
+/*    Zmp_distributor / zmp_interpolation / Force_torque_calculate         */
+/*    (:3650-3895) with the _nTdx > 3 tail of the ZMP roll-out (:938-951)  */
+/*    they read, and the 100-slot row (:288-392).  Not computed: KMP, foot */
+/*    rotation, XGetSolution_*, StartWalking / StopWalking (the node never */
+/*    calls them).                                                         */
+/* ====================================================================== */
+/* Defaults: NLPRTControlClass.h:16-18, NLPClass.h:37-38,
+ * NLPRTControlClass.cpp:34 and the "go1" _rad of Initialize (:275). */
+typedef struct qloco_nlp_node_params {
+  double dtx;                 /* 0.025  _dtx = dt_nlp; has to equal qloco_nlp_params.dt */
+  double height_offset_time;  /* 1 */
+  double height_squat_time;   /* 1 */
+  double height_offset;       /* 0      _height_offset of the squat polynomial */
+  double height_offsetx;      /* 0      _height_offsetx (only reaches _COM_IN, which nothing reads) */
+  double totalmass;           /* 12     RobotPara_totalmass = _mass */
+  double rad;                 /* 0.2    _j_ini = _mass * _rad^2 */
+  double reserved[9];
+} qloco_nlp_node_params;
+void qloco_nlp_node_params_default(qloco_nlp_node_params *p);
+/* The node's members live in a third device workspace of
+ * qloco_nlp_node_workspace_bytes(batch) bytes (-1 for batch <= 0): the record,
+ * field-major (field f of robot b at f * B + b), then the scratch the inner
+ * tick writes.  get_state / set_state move a dense record of
+ * QLOCO_NLP_NODE_STATE doubles per robot (integers and flags as doubles):
+ *   [0] count | [1] mpc_start (latched) | [2] _t_walkdtime_restart_flag |
+ *   [3] mpc_stop | [4:7] diagonal of _Co_L | [7:10] diagonal of _Co_R |
+ *   [10:154] a ring of QLOCO_NLP_NODE_RING entries of (tag, _zmpx_real,
+ *   _zmpy_real): array index k lives in entry k % QLOCO_NLP_NODE_RING and the
+ *   tag is the array index the entry holds (-1: none) |
+ *   [154:254] the last row: every member WalkingReactStepping packs
+ *   (PelvisPos, the feet, zmp_ref, F_L, F_R, M_L, M_R, bjx1, dcm_ref,
+ *   PelvisPosv / a, mpc_body(13..37), mpc_rlfoot_traj(6..17), mpc_stop,
+ *   right_support) lives in its slot of the row and nowhere else.
+ * The ring replaces the reference's _zmpx_real / _zmpy_real of _nsum entries,
+ * kept "as last written": a tick writes entries i .. i + _nTdx - 1 and reads
+ * i, i - 1, round(_tx(_bjx1-1)/_dt) - 2 and round((_tx+_td)(_bjx1-1)/_dt) - 1,
+ * the last two only in the double-support ticks of a step, so the span fits
+ * as section 15's does.  An index no tick has written reads 0 (Initialize,
+ * :526); one whose entry a later index has taken reads NaN (QLOCO_NAN).
+ * Scratch, in doubles from the end of the records (offset * B, [B * n] each,
+ * row-major): 0 com_traj (38) | 38 rlfoot_traj (18) | 56 com (18) |
+ * 74 vari_ini (4) | 78 the zero estimated_state (6) | 84 rfoot_feedback (2) |
+ * 86 lfoot_feedback (2) | 88 the _bjx1 and _td(1) of before the tick (2) |
+ * 90, as int32: t_int[B], right_support[B], section 14's sched[B*4],
+ * the tick's status[B], branch[B]. */
+#define QLOCO_NLP_NODE_RING 48
+#define QLOCO_NLP_NODE_STATE 254
+#define QLOCO_NLP_NODE_SCRATCH 94
+/* sched[B*8] (int32, optional): the branch, _walkdtime1, _t_int (0: section 15
+ * did not tick), bjx1, status, count, _nTdx (0 unless walking), the array
+ * index of ZMP_end (-1 unless Zmp_distributor interpolates). */
+#define QLOCO_NLP_NODE_SCHED_LEN 8
+#define QLOCO_NLP_NODE_NOT_STARTED 0
+#define QLOCO_NLP_NODE_SQUAT 1
+#define QLOCO_NLP_NODE_WALKING 2
+#define QLOCO_NLP_NODE_OVER_TIME 3
+#define QLOCO_NLP_NODE_STOPPED 4
+int64_t qloco_nlp_node_workspace_bytes(int64_t batch);
+/* qloco_nlp_tick_init on the first two workspaces, then NLPRTControlClass()
+ * (:86-185) on the third. */
+int qloco_nlp_node_init(const qloco_nlp_params *prm, const qloco_nlp_tick_params *tick_prm,
+                        const qloco_nlp_node_params *node_prm, int64_t batch, void *nlp_workspace,
+                        void *tick_workspace, void *node_workspace, const double *steplength,
+                        const double *stepwidth, const double *stepheight, void *stream);
+/* One iteration of the node loop of every robot, three launches on one stream
+ * and no host step: a kernel that reads nrt_msg[B*25] (the latest /rt2nrt/state
+ * row: [0] > 0 starts the robot and advances its count, [19..21] / [22..24] the
+ * left / right foot feedback), picks the branch and writes the t_int section 15
+ * takes (0 for a robot that does not walk this tick, which section 15 answers
+ * with QLOCO_BAD_SIZE and untouched records); qloco_nlp_tick, with zeros for
+ * estimated_state as rt_nlp_gait passes them; a kernel that writes
+ * gait_msg[B*100], the /MPC/Gait row ([98] = 0, the node's wall-clock duration).
+ * A stopped robot (mpc_stop >= 1) re-emits its last row.  status[B] (optional):
+ * QLOCO_OK, section 15's status of a walking robot, or QLOCO_NAN when a slot
+ * this section computes is not finite. */
+int qloco_nlp_node_tick(const qloco_nlp_params *prm, const qloco_nlp_tick_params *tick_prm,
+                        const qloco_nlp_node_params *node_prm, int64_t batch, void *nlp_workspace,
+                        void *tick_workspace, void *node_workspace, const double *nrt_msg,
+                        double *gait_msg, int32_t *sched, int32_t *status, void *stream);
+/* Form of the row store: 0 = each lane writes its robot's row, 1 = the wave
+ * stages 16 rows at a time through LDS and writes them coalesced (default);
+ * results do not depend on it.  Returns the previous value, or QLOCO_ERR_ARG. */
+int qloco_nlp_node_set_form(int form);
+/* Dense state[B * QLOCO_NLP_NODE_STATE] out of / into the third workspace. */
+int qloco_nlp_node_get_state(int64_t batch, const void *node_workspace, double *state, void *stream);
+int qloco_nlp_node_set_state(int64_t batch, void *node_workspace, const double *state, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

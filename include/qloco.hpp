@@ -27,6 +27,8 @@
  *   Go1ServoBatch                 <- one iteration of the go1 sim servo loop (go1_rt_control/
  *                                    src/servo_control/servo.cpp:675-1330)
  *   NLPClassBatch                 <- NLPClass::step_timing_opti_loop + Foot_trajectory_solve_mod2
+ *   NLPRTControlBatch             <- NLPRTControlClass::WalkingReactStepping and the node loop of
+ *                                    gait_nlp_kmp.cpp:101-158 (the /MPC/Gait row)
  *   NLPStepTimingBatch            <- NLPClass::step_timing_opti_loop (mosek_nlp_kmp/src/NLP/
  *                                    NLPClass_sqp.cpp:693-1102; NLPRTControlClass.cpp:445)
  *   Kinematicclass                <- go1_rt_control Kinematicclass
@@ -446,7 +448,7 @@ class NLPStepTimingBatch {
 // when j_index or stopwalking differ from it, or when no tick preceded it
 // (NLPRTControlClass.cpp:445-459 calls the two back to back with the same
 // arguments).  `lamda` is accepted and unused, as in the reference.
-// Zmp_distributor and the _state_generate_interpo packing stay on the host.
+// Zmp_distributor and the _state_generate_interpo packing are NLPRTControlBatch's.
 class NLPClassBatch {
  public:
   static constexpr int kComTraj = 38, kFootTraj = 18;
@@ -482,6 +484,59 @@ class NLPClassBatch {
   int32_t *d_i_, *d_int_;
   std::vector<int32_t> status_;
   std::vector<double> foot_;
+};
+
+// ------------------------------------------------------------------------
+// NLPRTControlClass (mosek_nlp_kmp/src/NLPRTControl/NLPRTControlClass.cpp) with
+// the node loop around it (gait_nlp_kmp.cpp:101-158), B robots: the start latch
+// and loop counter, the branch of WalkingReactStepping (not started, squat,
+// walking, over time), the planner tick, Zmp_distributor and the 100-slot
+// /MPC/Gait row, in one call with no host step (qloco_nlp_node_tick).  The
+// constructor mirrors NLPRTControlClass(): the "go1" step inputs (:63-80) and
+// the member setup (:86-185).  StartWalking / StopWalking are not modelled: the
+// node never calls them.
+class NLPRTControlBatch {
+ public:
+  static constexpr int kRow = QLOCO_GAIT_MSG_LEN;
+  explicit NLPRTControlBatch(int batch = 1, double stepheight = 0.0, const qloco_nlp_params *params = nullptr,
+                             const qloco_nlp_tick_params *tick_params = nullptr,
+                             const qloco_nlp_node_params *node_params = nullptr);
+  // B = 1, the reference's signature.  The node loop passes its counter and its
+  // latch; the device keeps both per robot and advances them from msg[0] > 0, so
+  // a call that continues the loop (walkdtime the last one or one more) costs no
+  // extra transfer and any other rewrites the two members first.  estimated_state
+  // is accepted and unused, as rt_nlp_gait passes its zero member instead (:445).
+  // Once mpc_stop >= 1 the last row is returned, as the loop re-publishes it.
+  std::array<double, 100> WalkingReactStepping(int walkdtime, bool start_mpc, const double estimated_state[18],
+                                               const double Rfoot_location_feedback[3],
+                                               const double Lfoot_location_feedback[3]);
+  // B robots, device pointers, asynchronous on stream(): nrt_msg[B*25] (the
+  // /rt2nrt/state rows: [0] > 0 starts a robot and advances its count) ->
+  // gait_msg[B*100]; sched[B*8] and status[B] (int32) may be NULL.  Chains with
+  // qloco_rt_tick and qloco_go1_servo_tick on the same buffers.
+  void tick(const double *d_nrt_msg, double *d_gait_msg, int32_t *d_sched = nullptr, int32_t *d_status = nullptr);
+  // dense member state: B * QLOCO_NLP_STATE, B * QLOCO_NLP_TICK_STATE and
+  // B * QLOCO_NLP_NODE_STATE doubles
+  void get_state(double *nlp_state, double *tick_state, double *node_state);
+  void set_state(const double *nlp_state, const double *tick_state, const double *node_state);
+  int right_support = 2;                         // robot 0, after the last B = 1 call
+  double mpc_stop = 0;
+  int status = QLOCO_OK;
+  int32_t sched[QLOCO_NLP_NODE_SCHED_LEN] = {0};
+  qloco_nlp_params params;
+  qloco_nlp_tick_params tick_params;
+  qloco_nlp_node_params node_params;
+  int batch() const { return batch_; }
+  void *stream() const { return arena_.stream(); }
+  void sync() { arena_.sync(); }
+
+ private:
+  int batch_, count_ = 0;
+  bool latch_ = false;
+  DeviceArena arena_;
+  void *d_ws_, *d_tws_, *d_nws_;
+  double *d_msg_, *d_row_, *d_rec_, *d_trec_, *d_nrec_;
+  int32_t *d_int_;
 };
 
 // ------------------------------------------------------------------------

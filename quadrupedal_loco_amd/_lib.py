@@ -92,6 +92,12 @@ class NlpTickParams(C.Structure):
     _fields_ = [("lift_height", C.c_double), ("hcom", C.c_double), ("reserved", C.c_double * 6)]
 
 
+class NlpNodeParams(C.Structure):
+    """Mirror of `qloco_nlp_node_params`."""
+    _fields_ = [(k, C.c_double) for k in ("dtx", "height_offset_time", "height_squat_time", "height_offset",
+                                          "height_offsetx", "totalmass", "rad")] + [("reserved", C.c_double * 9)]
+
+
 class ButterCoef(C.Structure):
     """Mirror of `qloco_butter_coef`."""
     _fields_ = [(k, C.c_double) for k in ("b0", "b1", "b2", "a1", "a2", "a")]
@@ -200,6 +206,15 @@ SIGNATURES = {
     "qloco_nlp_tick_set_group_width": (C.c_int, [C.c_int]),
     "qloco_nlp_tick_get_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_nlp_tick_set_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_node_params_default": (None, [C.POINTER(NlpNodeParams)]),
+    "qloco_nlp_node_workspace_bytes": (C.c_int64, [i64]),
+    "qloco_nlp_node_init": (C.c_int, [C.POINTER(NlpParams), C.POINTER(NlpTickParams), C.POINTER(NlpNodeParams),
+                                      i64] + [vp] * 7),
+    "qloco_nlp_node_tick": (C.c_int, [C.POINTER(NlpParams), C.POINTER(NlpTickParams), C.POINTER(NlpNodeParams),
+                                      i64] + [vp] * 8),
+    "qloco_nlp_node_set_form": (C.c_int, [C.c_int]),
+    "qloco_nlp_node_get_state": (C.c_int, [i64, vp, vp, vp]),
+    "qloco_nlp_node_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_go1_servo_params_default": (None, [C.POINTER(Go1ServoParams)]),
     "qloco_go1_servo_workspace_bytes": (C.c_int64, [i64]),
     "qloco_go1_servo_init": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, vp]),

@@ -36,6 +36,7 @@ SOURCES = [
     "qloco_a1ctrl.hip",
     "qloco_nlp.hip",
     "qloco_nlp_tick.hip",
+    "qloco_nlp_node.hip",
     "qloco_mgpu.hip",
     "qloco_gen.cpp",
     "qloco_srbd_tables.cpp",
@@ -48,7 +49,7 @@ SOURCES = [
 # Gauss-Jordan updates are written with explicit float2 ops).  Its pivot
 # loops are unrolled in full (static register per pivot column); the two-wave
 # inverse's body exceeds the default pragma-unroll budget, so it is raised.
-EXTRA = {"qloco_a1qp.hip": ["-ffp-contract=off"], "qloco_a1est.hip": ["-ffp-contract=off"], "qloco_a1ctrl.hip": ["-ffp-contract=off"], "qloco_nlp.hip": ["-ffp-contract=off"], "qloco_nlp_tick.hip": ["-ffp-contract=off"], "qloco_gi.hip": ["-ffp-contract=off"], "qloco_gi_wide.hip": ["-ffp-contract=off"], "qloco_force.hip": ["-ffp-contract=off"],
+EXTRA = {"qloco_a1qp.hip": ["-ffp-contract=off"], "qloco_a1est.hip": ["-ffp-contract=off"], "qloco_a1ctrl.hip": ["-ffp-contract=off"], "qloco_nlp.hip": ["-ffp-contract=off"], "qloco_nlp_tick.hip": ["-ffp-contract=off"], "qloco_nlp_node.hip": ["-ffp-contract=off"], "qloco_gi.hip": ["-ffp-contract=off"], "qloco_gi_wide.hip": ["-ffp-contract=off"], "qloco_force.hip": ["-ffp-contract=off"],
          "qloco_body.hip": ["-ffp-contract=off"], "qloco_rt.hip": ["-ffp-contract=off"], "qloco_servo.hip": ["-ffp-contract=off"], "qloco_go1_servo.hip": ["-ffp-contract=off"], "qloco_kin.hip": ["-ffp-contract=off"], "qloco_srbd.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"],
          "qloco_srbd_lit.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"]}
 
@@ -101,6 +102,7 @@ def build(verbose=False, jobs=8):
     build_a1_ctrl_host_test(verbose)
     build_nlp_host_test(verbose)
     build_nlp_tick_host_test(verbose)
+    build_nlp_node_host_test(verbose)
     build_go1_servo_host_test(verbose)
     return LIB
 
@@ -207,6 +209,24 @@ def build_nlp_tick_host_test(verbose=False):
     outdir = os.path.join(ROOT, "tests", "cpp", "_build")
     os.makedirs(outdir, exist_ok=True)
     exe = os.path.join(outdir, "test_nlp_tick_host")
+    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
+        return exe
+    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
+           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
+           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return exe
+
+
+def build_nlp_node_host_test(verbose=False):
+    """tests/cpp/test_nlp_node_host: the NLPRTControlBatch shim against the C
+    ABI (no oracle link)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_nlp_node_host.cpp")
+    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(outdir, exist_ok=True)
+    exe = os.path.join(outdir, "test_nlp_node_host")
     if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
         return exe
     cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [

@@ -1101,6 +1101,117 @@ void NLPClassBatch::set_state(const double *nlp_state, const double *tick_state)
 }
 
 // ------------------------------------------------------------------------
+// NLPRTControlBatch -> qloco_nlp_node_*
+NLPRTControlBatch::NLPRTControlBatch(int batch, double stepheight, const qloco_nlp_params *p,
+                                     const qloco_nlp_tick_params *tp, const qloco_nlp_node_params *np)
+    : batch_(positive_batch(batch, "NLPRTControlBatch")) {
+  if (p) params = *p;
+  else qloco_nlp_params_default(&params);
+  if (tp) tick_params = *tp;
+  else qloco_nlp_tick_params_default(&tick_params);
+  if (np) node_params = *np;
+  else qloco_nlp_node_params_default(&node_params);
+  const size_t B = batch;
+  const int64_t ws = qloco_nlp_workspace_bytes(batch), tws = qloco_nlp_tick_workspace_bytes(batch);
+  const int64_t nws = qloco_nlp_node_workspace_bytes(batch);
+  if (ws < 0 || tws < 0 || nws < 0) throw Error("qloco_nlp_node_workspace_bytes", QLOCO_ERR_ARG);
+  d_ws_ = arena_.alloc((size_t)ws);
+  d_tws_ = arena_.alloc((size_t)tws);
+  d_nws_ = arena_.alloc((size_t)nws);
+  d_msg_ = dalloc<double>(arena_, B * QLOCO_NRT_MSG_LEN);
+  d_row_ = dalloc<double>(arena_, B * kRow);
+  d_rec_ = dalloc<double>(arena_, B * QLOCO_NLP_STATE);
+  d_trec_ = dalloc<double>(arena_, B * QLOCO_NLP_TICK_STATE);
+  d_nrec_ = dalloc<double>(arena_, B * QLOCO_NLP_NODE_STATE);
+  d_int_ = dalloc<int32_t>(arena_, B * (QLOCO_NLP_NODE_SCHED_LEN + 1));
+  // stepwidthinput = 2 HALF_HIP_WIDTH, steplengthinput = 0.075 ("go1", NLPRTControlClass.cpp:63-71)
+  std::vector<double> in(3 * B);
+  for (size_t b = 0; b < B; ++b) {
+    in[b] = 0.075;
+    in[B + b] = params.half_hip_width * 2;
+    in[2 * B + b] = stepheight;
+  }
+  arena_.upload(d_rec_, in.data(), sizeof(double) * in.size());
+  abi_ok(qloco_nlp_node_init(&params, &tick_params, &node_params, batch_, d_ws_, d_tws_, d_nws_, d_rec_, d_rec_ + B,
+                             d_rec_ + 2 * B, arena_.stream()),
+         "qloco_nlp_node_init");
+  arena_.sync();
+}
+
+void NLPRTControlBatch::tick(const double *d_nrt_msg, double *d_gait_msg, int32_t *d_sched, int32_t *d_status) {
+  abi_ok(qloco_nlp_node_tick(&params, &tick_params, &node_params, batch_, d_ws_, d_tws_, d_nws_, d_nrt_msg,
+                             d_gait_msg, d_sched, d_status, arena_.stream()),
+         "qloco_nlp_node_tick");
+}
+
+std::array<double, 100> NLPRTControlBatch::WalkingReactStepping(int walkdtime, bool start_mpc,
+                                                                const double /*estimated_state*/[18],
+                                                                const double Rfoot[3], const double Lfoot[3]) {
+  if (batch_ != 1) throw Error("NLPRTControlBatch: the single-robot call needs batch 1", QLOCO_ERR_ARG);
+  if (!Rfoot || !Lfoot) throw Error("NLPRTControlBatch::WalkingReactStepping: null argument", QLOCO_ERR_ARG);
+  double msg[QLOCO_NRT_MSG_LEN] = {0};
+  if (start_mpc && walkdtime == count_ + 1) {
+    msg[0] = 1.0;  // the loop's own step: the device advances count and latch
+  } else if (!(start_mpc == latch_ && walkdtime == count_)) {
+    // any other caller: write the two members the loop would hold
+    std::vector<double> rec(QLOCO_NLP_NODE_STATE);
+    abi_ok(qloco_nlp_node_get_state(1, d_nws_, d_nrec_, arena_.stream()), "qloco_nlp_node_get_state");
+    arena_.download(rec.data(), d_nrec_, sizeof(double) * rec.size());
+    arena_.sync();
+    rec[0] = walkdtime;
+    rec[1] = start_mpc ? 1.0 : 0.0;
+    arena_.upload(d_nrec_, rec.data(), sizeof(double) * rec.size());
+    abi_ok(qloco_nlp_node_set_state(1, d_nws_, d_nrec_, arena_.stream()), "qloco_nlp_node_set_state");
+  }
+  count_ = walkdtime;
+  latch_ = start_mpc;
+  for (int k = 0; k < 3; ++k) {
+    msg[19 + k] = Lfoot[k];
+    msg[22 + k] = Rfoot[k];
+  }
+  arena_.upload(d_msg_, msg, sizeof(msg));
+  tick(d_msg_, d_row_, d_int_, d_int_ + QLOCO_NLP_NODE_SCHED_LEN);
+  std::array<double, 100> row;
+  int32_t ints[QLOCO_NLP_NODE_SCHED_LEN + 1];
+  arena_.download(row.data(), d_row_, sizeof(double) * kRow);
+  arena_.download(ints, d_int_, sizeof(ints));
+  arena_.sync();
+  for (int k = 0; k < QLOCO_NLP_NODE_SCHED_LEN; ++k) sched[k] = ints[k];
+  status = ints[QLOCO_NLP_NODE_SCHED_LEN];
+  mpc_stop = row[97];
+  right_support = (int)row[99];
+  return row;
+}
+
+void NLPRTControlBatch::get_state(double *nlp_state, double *tick_state, double *node_state) {
+  if (!nlp_state || !tick_state || !node_state) throw Error("NLPRTControlBatch::get_state: null output", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  abi_ok(qloco_nlp_get_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_get_state");
+  abi_ok(qloco_nlp_tick_get_state(batch_, d_tws_, d_trec_, arena_.stream()), "qloco_nlp_tick_get_state");
+  abi_ok(qloco_nlp_node_get_state(batch_, d_nws_, d_nrec_, arena_.stream()), "qloco_nlp_node_get_state");
+  arena_.download(nlp_state, d_rec_, sizeof(double) * B * QLOCO_NLP_STATE);
+  arena_.download(tick_state, d_trec_, sizeof(double) * B * QLOCO_NLP_TICK_STATE);
+  arena_.download(node_state, d_nrec_, sizeof(double) * B * QLOCO_NLP_NODE_STATE);
+  arena_.sync();
+}
+
+void NLPRTControlBatch::set_state(const double *nlp_state, const double *tick_state, const double *node_state) {
+  if (!nlp_state || !tick_state || !node_state) throw Error("NLPRTControlBatch::set_state: null input", QLOCO_ERR_ARG);
+  const size_t B = batch_;
+  arena_.upload(d_rec_, nlp_state, sizeof(double) * B * QLOCO_NLP_STATE);
+  arena_.upload(d_trec_, tick_state, sizeof(double) * B * QLOCO_NLP_TICK_STATE);
+  arena_.upload(d_nrec_, node_state, sizeof(double) * B * QLOCO_NLP_NODE_STATE);
+  abi_ok(qloco_nlp_set_state(batch_, d_ws_, d_rec_, arena_.stream()), "qloco_nlp_set_state");
+  abi_ok(qloco_nlp_tick_set_state(batch_, d_tws_, d_trec_, arena_.stream()), "qloco_nlp_tick_set_state");
+  abi_ok(qloco_nlp_node_set_state(batch_, d_nws_, d_nrec_, arena_.stream()), "qloco_nlp_node_set_state");
+  arena_.sync();
+  if (batch_ == 1) {
+    count_ = (int)node_state[0];
+    latch_ = node_state[1] != 0.0;
+  }
+}
+
+// ------------------------------------------------------------------------
 // Kinematicclass -> qloco_leg_fk / qloco_leg_ik
 Kinematicclass::Kinematicclass(int max_legs) : cap_(0) {
   if (max_legs < 1) throw Error("Kinematicclass: max_legs < 1", QLOCO_ERR_ARG);

@@ -18,12 +18,19 @@ chains on one stream with no copy.  `StepTimingPlanner` does not compute
 CoM_height_solve (and with it _comz, ZMP, DCM) or the foot trajectories;
 `PlannerTick` (`qloco_nlp_tick`, csrc/qloco_nlp_tick.hip) runs the same SQP
 kernel and adds them: the full 38-vector of step_timing_opti_loop and the
-18-vector and support flag of Foot_trajectory_solve_mod2.  KMP is not computed.
+18-vector and support flag of Foot_trajectory_solve_mod2.  `PlannerNode`
+(`qloco_nlp_node_tick`, csrc/qloco_nlp_node.hip) wraps that tick in the node
+loop: the /rt2nrt/state row in, the /MPC/Gait row out, so that
+
+    gait_msg = node.tick(nrt_msg).gait_msg
+    traj_msg, nrt_msg, *_ = rt_node.tick(gait_msg, ctrl_msg)
+
+closes the planner - rt loop on the device.  KMP is not computed.
 """
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import NlpParams, NlpTickParams, check, lib, ptr
+from ._lib import NlpNodeParams, NlpParams, NlpTickParams, check, lib, ptr
 from .a1est import _dev
 
 NS = 27               # QLOCO_NLP_STEPS
@@ -234,6 +241,127 @@ class PlannerTick(StepTimingPlanner):
         _dev(state, "f64", (self.batch, TICK_STATE), "state")
         check(lib().qloco_nlp_tick_set_state(self.batch, ptr(self.tick_workspace), ptr(state), self._stream(stream)),
               "qloco_nlp_tick_set_state")
+
+
+NODE_STATE = 254      # QLOCO_NLP_NODE_STATE
+NODE_RING = 48        # QLOCO_NLP_NODE_RING
+NODE_SCRATCH = 94     # QLOCO_NLP_NODE_SCRATCH
+NODE_SCHED_LEN = 8    # QLOCO_NLP_NODE_SCHED_LEN
+NODE_STATE_FIELDS = dict(  # slices of the dense record of the third workspace
+    count=(0, 1), latch=(1, 2), restart=(2, 3), mpc_stop=(3, 4), co_l=(4, 7), co_r=(7, 10), ring=(10, 154),
+    row=(154, 254))
+NODE_BRANCHES = ("not_started", "squat", "walking", "over_time", "stopped")   # sched[:, 0]
+GAIT_MSG_LEN, NRT_MSG_LEN = 100, 25
+
+
+def default_node_params(**overrides):
+    """NLPRTControlClass.h:16-18, NLPClass.h:37-38, RobotPara_totalmass and
+    the "go1" _rad."""
+    p = NlpNodeParams()
+    lib().qloco_nlp_node_params_default(C.byref(p))
+    for k, v in overrides.items():
+        if k == "reserved" or not hasattr(p, k):
+            raise ValueError("unknown parameter %s" % k)
+        setattr(p, k, v)
+    return p
+
+
+@dataclass
+class PlannerNodeResult:
+    gait_msg: object      # (B, 100): the /MPC/Gait row
+    sched: object         # (B, 8) int32: branch, _walkdtime1, _t_int, bjx1, status, count, _nTdx, ZMP_end index
+    status: object        # (B,) int32
+
+
+class PlannerNode(PlannerTick):
+    """Batched drop-in for one iteration of the slow planner node's loop
+    (gait_nlp_kmp.cpp:101-158 with NLPRTControlClass::WalkingReactStepping):
+    per robot the start latch and counter, the branch, `PlannerTick`'s tick
+    launched unchanged, Zmp_distributor and the 100-slot row.  The node's
+    members live in a third workspace (`get_node_state`)."""
+
+    def __init__(self, batch, device, params=None, tick_params=None, node_params=None, steplength=0.075,
+                 stepwidth=None, stepheight=None, **overrides):
+        import torch
+        self.node_params = node_params if node_params is not None else default_node_params()
+        nbytes = lib().qloco_nlp_node_workspace_bytes(int(batch))
+        if nbytes <= 0:
+            raise ValueError("qloco_nlp_node_workspace_bytes(%d) = %d" % (batch, nbytes))
+        self.node_workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=torch.device(device))
+        super().__init__(batch, device, params=params, tick_params=tick_params, steplength=steplength,
+                         stepwidth=stepwidth, stepheight=stepheight, **overrides)
+
+    def init(self, steplength, stepwidth, stepheight=None, stream=None):
+        """FootStepInputs + Initialize + NLPRTControlClass() of all three records."""
+        sl = self._per_robot(steplength, "steplength")
+        sw = self._per_robot(stepwidth, "stepwidth")
+        if stepheight is None:
+            stepheight = self._stepheight
+        sh = None if stepheight is None else self._per_robot(stepheight, "stepheight")
+        check(lib().qloco_nlp_node_init(C.byref(self.params), C.byref(self.tick_params), C.byref(self.node_params),
+                                        self.batch, ptr(self.workspace), ptr(self.tick_workspace),
+                                        ptr(self.node_workspace), ptr(sl), ptr(sw),
+                                        None if sh is None else ptr(sh), self._stream(stream)),
+              "qloco_nlp_node_init")
+
+    def planner_tick(self, *args, **kw):
+        """PlannerTick.tick on the same two records (the node record is not advanced)."""
+        return super().tick(*args, **kw)
+
+    def tick(self, nrt_msg, out=None, stream=None):
+        """One iteration of the node loop: nrt_msg (B, 25), the latest
+        /rt2nrt/state row of every robot (a device tensor; `qloco_rt_tick`'s
+        output as it is).  out: a PlannerNodeResult of an earlier call."""
+        import torch
+        B = self.batch
+        _dev(nrt_msg, "f64", (B, NRT_MSG_LEN), "nrt_msg")
+        if out is None:
+            out = PlannerNodeResult(self._f64(B, GAIT_MSG_LEN),
+                                    torch.empty((B, NODE_SCHED_LEN), dtype=torch.int32, device=self.device),
+                                    torch.empty((B,), dtype=torch.int32, device=self.device))
+        check(lib().qloco_nlp_node_tick(
+            C.byref(self.params), C.byref(self.tick_params), C.byref(self.node_params), B, ptr(self.workspace),
+            ptr(self.tick_workspace), ptr(self.node_workspace), ptr(nrt_msg), ptr(out.gait_msg), ptr(out.sched),
+            ptr(out.status), self._stream(stream)), "qloco_nlp_node_tick")
+        return out
+
+    def scratch(self):
+        """Views of what the inner tick of the last `tick` wrote: com_traj
+        (B, 38), rlfoot_traj (B, 18), com (B, 18), vari_ini (B, 4),
+        rfoot_feedback / lfoot_feedback (B, 2), prev (B, 2: the _bjx1 and
+        _td(1) of before the tick), and as int32 t_int (B,),
+        right_support (B,), sched (B, 4), status (B,), branch (B,)."""
+        import torch
+        B = self.batch
+        s = self.node_workspace[NODE_STATE * B:]
+        f = lambda off, n: s[off * B:(off + n) * B].view(B, n)
+        n = s[90 * B:94 * B].view(torch.int32)
+        return dict(com_traj=f(0, 38), rlfoot_traj=f(38, 18), com=f(56, 18), vari_ini=f(74, 4),
+                    rfoot_feedback=f(84, 2), lfoot_feedback=f(86, 2), prev=f(88, 2),
+                    t_int=n[:B], right_support=n[B:2 * B], sched=n[2 * B:6 * B].view(B, 4), status=n[6 * B:7 * B],
+                    branch=n[7 * B:8 * B])
+
+    def get_node_state(self, stream=None):
+        """Dense (B, 254) node record per robot (NODE_STATE_FIELDS)."""
+        s = self._f64(self.batch, NODE_STATE)
+        check(lib().qloco_nlp_node_get_state(self.batch, ptr(self.node_workspace), ptr(s), self._stream(stream)),
+              "qloco_nlp_node_get_state")
+        return s
+
+    def set_node_state(self, state, stream=None):
+        _dev(state, "f64", (self.batch, NODE_STATE), "state")
+        check(lib().qloco_nlp_node_set_state(self.batch, ptr(self.node_workspace), ptr(state), self._stream(stream)),
+              "qloco_nlp_node_set_state")
+
+
+def set_node_form(form):
+    """Form of the node's row store: 0 (each lane writes its robot's row) or 1
+    (16 rows at a time through LDS, coalesced; the default); returns the previous value.  A
+    throughput knob: results do not depend on it."""
+    r = lib().qloco_nlp_node_set_form(int(form))
+    if r == 100:
+        raise ValueError("form must be 0 or 1")
+    return r
 
 
 def set_group_width(gw):
