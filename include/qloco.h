@@ -231,7 +231,10 @@ int qloco_gen_srbd_host_strided(uint64_t seed, int32_t horizon, float dt, int32_
 /*    CI[n*m], ci0[m].  A NULL CE/ce0/CI/ci0 with stride 0 broadcasts one    */
 /*    shared copy; *_stride = elements between instances (0 = shared).     */
 /*    Outputs x[B*n], f[B] (cost, +inf when infeasible), status[B],         */
-/*    iters[B].                                                             */
+/*    iters[B]; f, status and iters may be NULL.  QLOCO_NOT_PD stores        */
+/*    x = 0, f = +inf, iters = 0.  More live (non-zero) CE columns than      */
+/*    variables report QLOCO_DEGENERATE at column n + 1, x as the first n    */
+/*    left it.                                                              */
 /* ====================================================================== */
 int qloco_eiquadprog_solve(int32_t n, int32_t p, int32_t m, int64_t batch, const double *G,
                            int64_t G_stride, const double *g0, int64_t g0_stride,

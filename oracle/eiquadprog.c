@@ -233,6 +233,7 @@ double qo_eqp_solve(qo_eqp_ws *w, double *G, const double *g0, const double *CE,
   if (!llt_lower(n, G, L)) {
     if (status) *status = QO_NOT_PD;
     if (iters) *iters = 0;
+    memset(x, 0, sizeof(double) * n); /* the reference leaves x untouched */
     return inf;
   }
   memcpy(G, L, sizeof(double) * (size_t)n * n); /* G is overwritten (hpp:45-48) */
@@ -290,7 +291,11 @@ double qo_eqp_solve(qo_eqp_ws *w, double *G, const double *g0, const double *CE,
     for (k = 0; k < iq; ++k) u[k] -= t2 * r[k];
     f_value += 0.5 * (t2 * t2) * znp;
     A[i] = -i - 1;
-    if (!add_constraint(w, &iq, &R_norm)) {
+    /* More live equality columns than variables: the reference's
+     * add_constraint would write column n of its n x n R and read d(n), out
+     * of bounds.  z is zero here (update_z over no columns), so t2 = 0 and
+     * x, f are unchanged; report what a zero d(n) gives, degenerate. */
+    if (iq == n || !add_constraint(w, &iq, &R_norm)) {
       if (status) *status = QO_DEGENERATE;
       if (iters) *iters = iter;
       return f_value;

@@ -44,6 +44,12 @@ __global__ __launch_bounds__(64) void gi_kernel(const GiArgs a) {
                  a.CE ? a.CE + inst * a.sCE : nullptr, a.ce0 ? a.ce0 + inst * a.sce0 : nullptr,
                  a.CI ? a.CI + inst * a.sCI : nullptr, a.ci0 ? a.ci0 + inst * a.sci0 : nullptr,
                  a.x + inst * a.n, f, st, it);
+  // Cholesky failed before x was formed: the core stored LDS it never wrote
+  // (same lanes, same rows), so the defined output is x = 0 (qloco.h).
+  // Done here and not at the core's done: label, because the step-timing
+  // kernel seeds the core's x and reads it back after a failed Cholesky
+  if (st == QLOCO_NOT_PD)
+    for (int k = li; k < a.n; k += 16) a.x[inst * a.n + k] = 0.0;
   if (li == 0) {
     if (a.f) a.f[inst] = f;
     if (a.status) a.status[inst] = st;

@@ -409,7 +409,11 @@ __device__ void gw_solve(GwLds L, int li, int n, int p, int m, const double *G, 
       }
       GW_SYNC();
       f_value += 0.5 * (t2 * t2) * znp;
-      if (!g.add_constraint(iq, R_norm)) {
+      // more live equality columns than variables: add_constraint would
+      // write column n of R (the start of L.x) and read d[n] (np[0]).  z is
+      // zero here, so x and f are unchanged; report what the 16-lane core's
+      // zeroed d slot gives, degenerate (oracle/eiquadprog.c does the same)
+      if (iq == n || !g.add_constraint(iq, R_norm)) {
         status = QLOCO_DEGENERATE;
         goto done;
       }
@@ -583,7 +587,8 @@ __device__ void gw_solve(GwLds L, int li, int n, int p, int m, const double *G, 
 
 done:
   GW_SYNC();
-  if (li < n) xout[li] = L.x[li];
+  // L.x is unwritten when Cholesky failed: the defined output is x = 0
+  if (li < n) xout[li] = status == QLOCO_NOT_PD ? 0.0 : L.x[li];
   f_out = f_value;
   status_out = status;
   iters_out = iter;

@@ -25,19 +25,29 @@ def _stream(t):
     return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
 
 
-def eiquadprog_solve(G, g0, CE, ce0, CI, ci0, n, p, m):
+def _eqp_batch(operands, batch=None):
+    """The batch size of an eiquadprog_solve call: `batch` if given, else the
+    rows of the first 2-D operand (1-D operands are shared by all instances)."""
+    stacked = [t.shape[0] for t in operands if t is not None and t.dim() == 2]
+    if batch is None:
+        if not stacked:
+            raise ValueError("every operand is 1-D (shared): pass batch=")
+        batch = stacked[0]
+    if any(b != batch for b in stacked):
+        raise ValueError("stacked operands disagree on the batch size: %s vs %d" % (stacked, batch))
+    return int(batch)
+
+
+def eiquadprog_solve(G, g0, CE, ce0, CI, ci0, n, p, m, batch=None):
     """Batched solve of min 0.5x'Gx + g0'x s.t. CE'x + ce0 = 0, CI'x + ci0 >= 0.
 
     Each argument is (B, k) float64 with column-major matrices flattened per
-    instance (Eigen storage), or a 1-D tensor shared by all instances.
-    Returns dict(x, f, status, iters)."""
+    instance (Eigen storage), or a 1-D tensor shared by all instances.  B is
+    the first 2-D operand's row count, or `batch` (required when every
+    operand is shared).  Returns dict(x, f, status, iters)."""
     import torch
-    B = G.shape[0]
-    dev = G.device
-    out = {"x": torch.empty((B, n), dtype=torch.float64, device=dev),
-           "f": torch.empty(B, dtype=torch.float64, device=dev),
-           "status": torch.empty(B, dtype=torch.int32, device=dev),
-           "iters": torch.empty(B, dtype=torch.int32, device=dev)}
+    B = _eqp_batch([G, g0, CE if p else None, ce0 if p else None, CI if m else None,
+                    ci0 if m else None], batch)
 
     def sd(t, k):
         if t is None:
@@ -45,6 +55,8 @@ def eiquadprog_solve(G, g0, CE, ce0, CI, ci0, n, p, m):
         t = t.contiguous()
         if t.dtype != torch.float64:
             raise ValueError("float64 expected")
+        if t.dim() not in (1, 2) or t.shape[-1] != k:
+            raise ValueError("operand of shape %s: expected (B, %d) or (%d,)" % (tuple(t.shape), k, k))
         return t, (0 if t.dim() == 1 else k)
 
     Gt, sG = sd(G, n * n)
@@ -53,6 +65,11 @@ def eiquadprog_solve(G, g0, CE, ce0, CI, ci0, n, p, m):
     ce0t, sce0 = sd(ce0 if p else None, p)
     CIt, sCI = sd(CI if m else None, n * m)
     ci0t, sci0 = sd(ci0 if m else None, m)
+    dev = G.device
+    out = {"x": torch.empty((B, n), dtype=torch.float64, device=dev),
+           "f": torch.empty(B, dtype=torch.float64, device=dev),
+           "status": torch.empty(B, dtype=torch.int32, device=dev),
+           "iters": torch.empty(B, dtype=torch.int32, device=dev)}
     check(lib().qloco_eiquadprog_solve(n, p, m, B, ptr(Gt), sG, ptr(gt), sg, ptr(CEt), sCE,
                                        ptr(ce0t), sce0, ptr(CIt), sCI, ptr(ci0t), sci0,
                                        ptr(out["x"]), ptr(out["f"]), ptr(out["status"]),

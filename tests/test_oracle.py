@@ -336,6 +336,147 @@ def test_eiquadprog_matches_slsqp_random():
         assert np.allclose(x, res.x, atol=1e-5)
 
 
+# ---- preconditions of the QP input families (tests/qp_cases.py), asserted on
+# the restatement alone so that no family can quietly turn into inputs that
+# never solve; tests/test_qp_gpu.py runs the same inputs on the device.
+import qp_cases as Q  # noqa: E402
+
+
+@pytest.mark.parametrize("n,p,m,zero_ce", Q.FAMILY_A)
+def test_qp_family_a_mostly_solves(n, p, m, zero_ce):
+    """Feasible Gaussian QPs: OK on at least 3/4 of the 64 instances and the
+    active set works (mean iterations > 2).  Measured: 64, 64, 63, 64 OK;
+    mean iterations 11.0, 8.0, 15.4, 17.2."""
+    _, sol = Q.family_a(n, p, m, zero_ce)
+    assert sol.census().get(Q.OK, 0) >= 48, sol.census()
+    assert set(sol.census()) <= {Q.OK, Q.INFEASIBLE}
+    assert sol.iters[sol.status == Q.OK].mean() > 2
+
+
+@pytest.mark.parametrize("n", Q.FAMILY_B)
+def test_qp_family_b_closed_form(n):
+    """Box QPs: all 64 OK, an active set for n >= 4, and the restatement
+    within qp_cases.BOX_ERR[n] of clip(-g0 / diag G, lo, hi)."""
+    _, sol, xc = Q.family_b(n)
+    assert sol.census() == {Q.OK: 64}
+    assert sol.iters.mean() > (2 if n >= 4 else 1)
+    err = np.abs(sol.x - xc).max()
+    assert err <= Q.BOX_ERR[n], (n, err)
+
+
+# sum and CRC-32 of the 64 iteration counts (little-endian int32), per shape
+TIE_PINS = {(4, 8): (247, 1991256451), (8, 24): (525, 2127935183), (16, 64): (1154, 1869969924),
+            (17, 65): (1227, 436725330), (32, 96): (2098, 359806586)}
+
+
+@pytest.mark.parametrize("n,m", Q.FAMILY_C)
+def test_qp_family_c_ties_are_pinned(n, m):
+    """Coupled-tie QPs: all 64 OK, and the iteration counts are the pinned
+    ones.  With these counts an instrumented copy of the restatement (kept
+    out of the repository) met an exact tie in the most-violated scan on
+    14 / 19 / 38 / 32 / 58 of the 64 instances at (4,8) (8,24) (16,64)
+    (17,65) (32,96), and a copy whose scan keeps the LAST tied index changed
+    status or iterations on 3 / 7 / 13 / 19 / 33 of them -- so these pins,
+    and the GPU test's iteration equality, hold the tie rule (first index of
+    the strict minimum).  The inputs are small integers and powers of two
+    drawn without floating-point arithmetic, so the pins do not depend on
+    the platform's BLAS."""
+    probs, sol = Q.family_c(n, m)
+    assert sol.census() == {Q.OK: 64}
+    assert (int(sol.iters.sum()), sol.iters_crc()) == TIE_PINS[n, m]
+    for G, g0, _, _, CI, ci0 in probs[:4]:  # the data are what the docstring says
+        assert np.all(np.isin(np.abs(-g0 / np.diag(G)), (4.0, 8.0)))
+        assert np.all(np.isin((CI != 0).sum(axis=0), (2, 3))) and np.all(np.isin(ci0, (1.0, 2.0)))
+    # x = 0 is strictly feasible, and the result is feasible and no worse
+    for (G, g0, _, _, CI, ci0), x, f in zip(probs, sol.x, sol.f):
+        assert np.all(CI.T @ x + ci0 >= -1e-9) and f <= 1e-9
+
+
+def test_qp_family_d_census():
+    """Mixed statuses: instance b is NOT_PD / INFEASIBLE / OK with an active
+    set / OK after one iteration for b mod 4 = 0 / 1 / 2 / 3, B = 67."""
+    _, sol = Q.family_d()
+    assert len(sol.status) == 67
+    for b in range(67):
+        kind = Q.FAMILY_D_KINDS[b % 4]
+        want = {"not_pd": Q.NOT_PD, "infeasible": Q.INFEASIBLE}.get(kind, Q.OK)
+        assert sol.status[b] == want, (b, kind, sol.status[b])
+        if kind == "not_pd":
+            assert sol.iters[b] == 0 and np.isinf(sol.f[b]) and np.all(sol.x[b] == 0.0)
+        if kind == "infeasible":
+            assert np.isinf(sol.f[b]) and sol.iters[b] >= 1
+        if kind == "active":
+            assert sol.iters[b] > 1
+        if kind == "slack":
+            assert sol.iters[b] == 1
+
+
+@pytest.mark.parametrize("n,p", Q.FAMILY_E)
+def test_qp_family_e_kkt(n, p):
+    """Equality-only QPs: all 64 OK after one iteration, and the restatement
+    within qp_cases.KKT_ERR of the KKT solution, relative to max(1, |x|max)."""
+    probs, sol, xk = Q.family_e(n, p)
+    assert sol.census() == {Q.OK: 64} and np.all(sol.iters == 1)
+    err = (np.abs(sol.x - xk).max(axis=1) / np.maximum(1.0, np.abs(xk).max(axis=1))).max()
+    assert err <= Q.KKT_ERR[n, p], (n, p, err)
+    for (G, g0, CE, ce0, _, _), x in zip(probs[:8], xk):  # the reference satisfies its equalities
+        assert np.abs(CE.T @ x + ce0).max() <= 1e-11 * max(1.0, np.abs(x).max())
+
+
+@pytest.mark.parametrize("n,p,m", Q.OVERFULL)
+def test_eiquadprog_more_live_equalities_than_variables(n, p, m):
+    """p > n live CE columns: the reference's add_constraint would be entered
+    with iq == n and write column n of its n x n R.  The restatement reports
+    QO_DEGENERATE there (what a zero d(n) gives), with 0 iterations and x as
+    the first n equalities left it: they hold, the rest cannot."""
+    probs, sol = Q.overfull(n, p, m)
+    assert sol.census() == {Q.DEGENERATE: len(probs)} and np.all(sol.iters == 0)
+    for (G, g0, CE, ce0, _, _), x in zip(probs, sol.x):
+        res = CE.T @ x + ce0
+        assert np.abs(res[:n]).max() <= 1e-9 * max(1.0, np.abs(x).max())
+        assert np.abs(res[n:]).max() > 1e-6
+
+
+@pytest.mark.parametrize("n,p,m,zero_ce", Q.EDGES)
+def test_qp_edge_shapes_solve(n, p, m, zero_ce):
+    """The edge / dispatch-boundary shapes of the GPU test: every instance
+    OK, except at (16, 16, 64) with two zero CE columns, where the me = p /
+    A(i) quirks turn some into INFEASIBLE reports (measured 35 OK, 29 not)."""
+    _, sol = Q.edge(n, p, m, zero_ce)
+    if (n, p, m) == (16, 16, 64):
+        assert set(sol.census()) == {Q.OK, Q.INFEASIBLE} and sol.census()[Q.OK] >= 16
+    else:
+        assert sol.census() == {Q.OK: 64}
+    if m == 0:
+        assert np.all(sol.iters == 1)
+
+
+def test_eiquadprog_solve_batch_from_first_stacked_operand():
+    """qp.eiquadprog_solve's batch size: the rows of the first 2-D operand
+    (a shared, 1-D G used to give B = n * n), or batch=; every operand 1-D
+    and no batch= is an error, and so are stacked operands that disagree.
+    Argument handling only: no device work."""
+    torch = pytest.importorskip("torch")
+    from quadrupedal_loco_amd import qp
+    n, p, m, B = 4, 1, 6, 5
+    G1, G2 = torch.zeros(n * n, dtype=torch.float64), torch.zeros(B, n * n, dtype=torch.float64)
+    g1, g2 = torch.zeros(n, dtype=torch.float64), torch.zeros(B, n, dtype=torch.float64)
+    CI2 = torch.zeros(B, n * m, dtype=torch.float64)
+    assert qp._eqp_batch([G2, g2, None, None, CI2, None]) == B
+    assert qp._eqp_batch([G1, g2, None, None, None, None]) == B       # shared G
+    assert qp._eqp_batch([G1, g1, None, None, CI2, None]) == B
+    assert qp._eqp_batch([G1, g1, None, None, None, None], batch=7) == 7
+    assert qp._eqp_batch([G2, g1, None, None, None, None], batch=B) == B
+    with pytest.raises(ValueError):
+        qp._eqp_batch([G1, g1, None, None, None, None])
+    with pytest.raises(ValueError):
+        qp._eqp_batch([G2, g2[:3], None, None, None, None])
+    with pytest.raises(ValueError):
+        qp._eqp_batch([G2, g1, None, None, None, None], batch=B + 1)
+    with pytest.raises(ValueError):  # all shared, through the public function, before any device call
+        qp.eiquadprog_solve(G1, g1, None, None, None, None, n=n, p=0, m=0)
+
+
 def test_persistent_solver_restatement_semantics():
     """oracle/persist.c (the reference's member OSQP solver, A1RobotControl.cpp:
     556-578, on the stance-only QP): the first call is the cold solve; an
