@@ -276,7 +276,18 @@ void qloco_force_params_default(qloco_force_params *p);
  * Per-instance state (in/out, double): F_leg_ref[B*12] (3x4 col-major),
  *   grf_opt[B*12] (previous solution = F_prev of q_goal, :305).
  * Outputs: F_leg_guess[B*12], qp_solution[B] (int32, 1 = no NaN),
- *   status[B] (EiQuadProg outcome), iters[B]. */
+ *   status[B] (EiQuadProg outcome), iters[B].
+ * qp_solution 0 (a NaN in the solution: status stays QLOCO_OK) stores
+ *   grf_opt = F_leg_guess (:364-367).
+ * Failed factorisation (status QLOCO_NOT_PD, iters 0: a non-positive or NaN
+ *   Cholesky pivot, e.g. a NaN or Inf base_p[0] or foot x, or alpha = beta =
+ *   gamma = 0): as in the reference, where solve_quadprog returns before it
+ *   touches _X = grf_opt (:386-392, :437-443, EiQuadProg.cpp:505-510),
+ *   grf_opt keeps its value from before the call, bit for bit, and
+ *   qp_solution is 1 unless that carried vector holds a NaN (then grf_opt =
+ *   F_leg_guess as above).  Unlike qloco_eiquadprog_solve, no x = 0 here.
+ *   Departure from Eigen: a NaN pivot counts as failed (!(pivot > 0)); Eigen's
+ *   LLT would run on to a NaN solution and the F_leg_guess fallback. */
 int qloco_force_qp_solve(const qloco_force_params *prm, int64_t batch, const double *com_des,
                          const double *leg_des, const double *F_force_des,
                          const double *rfoot_des, const double *lfoot_des,
@@ -353,7 +364,13 @@ int qloco_joint_torques(int64_t batch, const double *Jaco, const int32_t *swing,
 int qloco_body_state_init_host(int64_t batch, double *state);
 /* i[B] (loop counter, int32), bodyangle_state[B*4], zmp_ref/angle_ref/
  * rfoot_ref/lfoot_ref[B*10] (Eigen 2x5 col-major), comacc_ref[B*15] (3x5)
- * -> com_traj[B*14]; state in/out; status[B] EiQuadProg outcome. */
+ * -> com_traj[B*14]; state in/out; status[B] EiQuadProg outcome.
+ * QLOCO_NOT_PD: G is positive definite for finite inputs (constants plus
+ * (j_ini / (mass (comacc_z + g)))^2 >= 0 on the diagonal), so only a NaN
+ * comacc_ref z in the horizon fails, through the NaN-pivot rule of section
+ * 3.  _X = _V_ini then stays as it was before the call, which is what the
+ * reference's failed solve leaves (:803, :843-847), and the post-processing
+ * runs on it. */
 int qloco_body_mpc_step(int64_t batch, const int32_t *i, const double *bodyangle_state,
                         const double *zmp_ref, const double *angle_ref,
                         const double *rfoot_ref, const double *lfoot_ref,

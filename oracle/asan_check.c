@@ -79,6 +79,8 @@ static int check_eiquadprog(void) {
   return runs;
 }
 
+static int force_not_pd = 0; /* NOT_PD calls seen by check_force_qp */
+
 static int check_force_qp(const char *dir) {
   size_t bytes = 0;
   unsigned char *buf = (unsigned char *)load(dir, "force.bin", &bytes);
@@ -102,8 +104,16 @@ static int check_force_qp(const char *dir) {
        * feet 30:42 FT 42:48 y 48 (49..51 pad) */
       qo_force_distribution(&s, d, d + 3, d + 15, mr[0], d[48], d + 21, d + 24);
       int est = 0, it = 0;
+      double before[12];
+      memcpy(before, s.grf_opt, sizeof(before));
       qo_force_opt(&s, &prm, d + 27, d + 30, d + 33, d + 36, d + 39, d + 42, mr[0], mr[1], d[48],
                    &est, &it);
+      /* a NaN / Inf base position (tests/force_cases.py bad_position): the
+       * failed factorisation keeps grf_opt */
+      if (est == QO_NOT_PD) {
+        if (it != 0 || memcmp(before, s.grf_opt, sizeof(before)) != 0) { qo_dyn_free(&s); free(buf); return -1; }
+        force_not_pd++;
+      }
       double tau[3], J[9], pd[3] = {0.1, 0.0, -0.3}, pe[3] = {0.1, 0.01, -0.29}, v[3] = {0, 0, 0};
       for (int k = 0; k < 9; ++k) J[k] = U(-0.3, 0.3);
       for (int leg = 0; leg < 4; ++leg) qo_compute_joint_torques(&s, J, leg & 1, pd, pe, v, v, leg, tau);
@@ -278,7 +288,7 @@ int main(int argc, char **argv) {
   const int a = check_a1();
   const int v = check_servo();
   const int k = check_kin_support();
-  printf("asan_check: eiquadprog %d, force_qp %d, rt %d, srbd %d, a1 %d, servo %d, kin+support %d\n",
-         e, f, r, s, a, v, k);
+  printf("asan_check: eiquadprog %d, force_qp %d (not_pd %d), rt %d, srbd %d, a1 %d, servo %d, kin+support %d\n",
+         e, f, force_not_pd, r, s, a, v, k);
   return (f < 0 || r < 0) ? 3 : 0;
 }

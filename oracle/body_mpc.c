@@ -224,6 +224,10 @@ int qo_body_theta_mpc(qo_body_state *s, int i, const double bodyangle_state[4],
       int st = QO_OK;
       qo_eqp_solve(s->ws, G, g0, NULL, NULL, CI, ci0, X, &st, NULL);
       if (eqp_status) *eqp_status = st;
+      /* Failed LLT (G holds pth^2: a NaN comacc_ref): solve_quadprog returns
+       * before it touches x (EiQuadProg.cpp:505-510), so _X still holds _V_ini.
+       * qo_eqp_solve's own contract is x = 0 there. */
+      if (st == QO_NOT_PD) memcpy(X, s->V_ini, sizeof(X));
       int ok = 1;
       for (int k = 0; k < NT; ++k)
         if (isnan(X[k])) { ok = 0; break; }

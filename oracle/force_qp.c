@@ -193,6 +193,9 @@ int qo_force_opt(qo_dyn_state *s, const qo_force_params *prm, const double base_
   int st = QO_OK;
   qo_eqp_solve(s->ws, Gs, g0, CE, ce0, CI, qph, X, &st, iters);
   if (eqp_status) *eqp_status = st;
+  /* Failed LLT: solve_quadprog returns before it touches x (EiQuadProg.cpp:505-510),
+   * so _X still holds grf_opt.  qo_eqp_solve's own contract is x = 0 there. */
+  if (st == QO_NOT_PD) memcpy(X, s->grf_opt, sizeof(X));
   /* QPBaseClass::solveQP: success iff no NaN in X (go1_rt_control QPBaseClass.cpp:116-142) */
   int ok = 1;
   for (int i = 0; i < 12; ++i)

@@ -302,6 +302,11 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void bo
       P.ci0[(2 * bp + 1) * BNH + row] = e1;
       P.ci0[8 * BNH + e] = 0.0;
     }
+    // _X = _V_ini (:803).  G holds pth^2 = (j_ini / (mass (acc_z + g)))^2, so a
+    // NaN comacc_ref makes the Cholesky fail; the solver then returns before
+    // it forms x (EiQuadProg.cpp:505-510) and the core hands back what gi.x
+    // held: seeded, the carried _V_ini as in the reference, not unwritten LDS
+    if (li < BNT) P.gi.x[li] = st[4 + li];
     GI_SYNC();
     double f;
     int it;

@@ -304,7 +304,13 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kForceWpe)))
       double atf = 0.0;
       const double *FT = a.FT_total_des + inst * 6;
       for (int k = 0; k < 6; ++k) atf += PA[r * 6 + k] * FT[k];
-      Pg0[r] = -2.0 * (a.alpha * atf + a.beta * guess[v] + a.gamma * a.grf_opt[inst * 12 + r]);
+      const double prev = a.grf_opt[inst * 12 + r];
+      Pg0[r] = -2.0 * (a.alpha * atf + a.beta * guess[v] + a.gamma * prev);
+      // _X = grf_opt (:391).  A failed Cholesky leaves the solver before it
+      // forms x (EiQuadProg.cpp:505-510) and the core then hands back what
+      // gi.x held: seeded, that is the carried grf_opt -- the reference's
+      // result -- and not LDS this block never wrote.
+      P.gi.x[r] = prev;
     }
   }
   GI_SYNC();

@@ -550,3 +550,204 @@ def test_persistent_literal_restatement_takes_update_path():
                 switch_it.append(info.iters)
                 cold_it.append(Instance(sp, x0, xr, ft, ct).admm_full()[1].iters)
     assert switch_it and np.mean(switch_it) < 0.7 * np.mean(cold_it), (switch_it, cold_it)
+
+
+# ---- force-QP and body-MPC input families (tests/force_cases.py, body_cases.py):
+# each family's precondition on the restatement alone, so that a generator
+# which stops reaching its branch fails here and not silently on the GPU
+
+import body_cases as BC  # noqa: E402
+import force_cases as FC  # noqa: E402
+
+
+def _force_family(name):
+    ticks, run = FC.family(name)
+    prm = [FC.oracle_params(**over) for _, over in ticks]
+    return ticks, run.ticks, prm
+
+
+@pytest.mark.parametrize("name", ["baseline", "heavy", "lateral", "hw_heavy", "hw_lateral"])
+def test_force_family_active_rows(name):
+    """Seed 3, B = 64, two ticks; measured census (tick 0 / tick 1), every
+    solve OK with qp_solution 1:
+      baseline    robots with no swing-leg rows (double support) 29 / 36, of
+                  them at >= 4 iterations 12 / 26 (up to 7); no leg at fz_max
+      heavy       a leg at fz_max on 47 / 55 robots (the rest stand on four
+                  legs at 4 m g / 4 < fz_max), 1-5 iterations
+      lateral     a friction row at equality on 64 / 64, 3-8 / 3-9 iterations
+      hw_heavy    fz_max on 47 / 55, 1-3 iterations (mu 0.5: no friction row)
+      hw_lateral  friction on 64 / 64, 3-8 / 3-9 iterations"""
+    ticks, res, prm = _force_family(name)
+    assert len(ticks) == 2
+    want = {"baseline": ((12, 0, 0), (26, 0, 0)), "heavy": ((0, 47, 0), (0, 55, 0)),
+            "lateral": ((29, 0, 64), (36, 0, 64)), "hw_heavy": ((0, 47, 0), (0, 55, 0)),
+            "hw_lateral": ((29, 0, 64), (36, 0, 64))}[name]
+    for t, ((d, _), r) in enumerate(zip(ticks, res)):
+        assert np.all(r["status"] == FC.OK) and np.all(r["qp_solution"] == 1), (name, t)
+        assert np.all(np.isfinite(r["grf_opt"]))
+        top, _, fr = FC.active_rows(r["grf_opt"], prm[t].fz_max, prm[t].mu)
+        pat0 = FC.pattern(d["mode"], d["right_support"]) == 0
+        deep = int(np.sum(r["iters"][pat0] >= 4))
+        print(name, t, "double support at >= 4 iterations", deep, "fz_max", int(np.sum(top > 0)),
+              "friction", int(np.sum(fr > 0)), "iterations", r["iters"].min(), r["iters"].max())
+        assert deep >= want[t][0] and int(np.sum(top > 0)) >= want[t][1] and int(np.sum(fr > 0)) >= want[t][2]
+        if name == "baseline":
+            assert int(np.sum(top > 0)) == 0
+        if name.endswith("heavy"):
+            assert r["iters"].max() >= 3
+        if name.endswith("lateral"):
+            assert r["iters"].min() >= 3 and r["iters"].max() >= 8
+    assert (prm[0].mass, prm[0].mu) == ((14.0, 0.5) if name.startswith("hw_") else (12.0, 0.25))
+
+
+@pytest.mark.parametrize("name", ["bad_position", "zero_weights"])
+def test_force_family_failed_factorisation_keeps_grf_opt(name):
+    """The force block's failed-factorisation result (include/qloco.h, as the
+    reference: dynmics_compute.cpp:386-392, :437-443, EiQuadProg.cpp:505-510):
+    status NOT_PD, 0 iterations, grf_opt bit-equal to its value before the
+    call -- a non-zero vector, the failing tick follows a healthy one -- and
+    qp_solution 1.  bad_position: the 16 robots with a NaN and the 16 with a
+    +Inf base_p[0], the other 32 OK; zero_weights: all 64.  The third tick
+    (healthy inputs) solves OK on all 64 from the carried vector."""
+    ticks, res, _ = _force_family(name)
+    assert len(ticks) == 3
+    B = FC.BATCH
+    bad = np.zeros(B, bool)
+    if name == "bad_position":
+        n, i = FC.bad_rows(B)
+        assert len(n) == len(i) == 16
+        assert np.all(np.isnan(ticks[1][0]["base_p"][n, 0])) and np.all(np.isposinf(ticks[1][0]["base_p"][i, 0]))
+        assert np.all(np.isfinite(ticks[1][0]["com_des"]))
+        bad[n] = bad[i] = True
+    else:
+        bad[:] = True
+    assert np.all(res[0]["status"] == FC.OK) and np.all(res[2]["status"] == FC.OK)
+    r = res[1]
+    assert np.array_equal(r["status"], np.where(bad, FC.NOT_PD, FC.OK))
+    assert np.all(r["iters"][bad] == 0) and np.all(r["iters"][~bad] >= 1)
+    assert np.all(r["qp_solution"] == 1)
+    assert r["grf_opt"][bad].tobytes() == r["grf_before"][bad].tobytes()
+    assert np.array_equal(r["grf_before"], res[0]["grf_opt"])
+    assert np.all(np.abs(r["grf_before"][bad]).max(axis=1) > 1.0)  # "unchanged" is not zero
+    assert np.all(np.isfinite(r["F_leg_guess"]))
+    assert np.array_equal(res[2]["grf_before"][bad], r["grf_before"][bad])
+
+
+def test_force_family_alpha0_closed_form():
+    """alpha = 0: G = 2 (beta + gamma) I; all 64 OK on both ticks.  Where
+    the blend (beta F_leg_guess + gamma grf_opt) / (beta + gamma), swing legs
+    zeroed, satisfies every inequality -- 43 and 30 robots, one iteration
+    each -- it is the solution, and the restatement is within 1.42e-14 N of
+    it (forces up to 105 N).  On the other robots the friction pyramid
+    couples fx, fy and fz (no clip): parity only."""
+    ticks, res, _ = _force_family("alpha0")
+    for t, ((d, over), r) in enumerate(zip(ticks, res)):
+        assert np.all(r["status"] == FC.OK) and np.all(r["qp_solution"] == 1)
+        x, rows = FC.alpha0_closed_form(d, over, r)
+        err = np.abs(r["grf_opt"][rows] - x[rows]).max()
+        print("alpha0 tick %d: closed form on %d robots, restatement error %.3g" % (t, len(rows), err))
+        assert len(rows) >= (43, 30)[t] and np.all(r["iters"][rows] == 1)
+        assert err <= 2e-14, (t, err)
+        assert r["iters"].max() >= 5  # the coupled robots work the active set
+
+
+def test_force_family_nan_demand_falls_back_and_carries():
+    """NaN in one entry of FT_total_des (and of F_force_des, the same array in
+    force_inputs) on the 16 robots b % 4 == 0, tick 0 only: the solve runs
+    (status OK, one iteration) to a NaN solution, qp_solution 0, grf_opt =
+    F_leg_guess position for position -- which holds the NaN on the 12 robots
+    in modes 101 / 102 (mode 103 leaves F_leg_ref alone).  Those 12 stay at
+    qp_solution 0 on the healthy tick 1, because gamma grf_opt carries the
+    NaN into g0, and 2 of them on tick 2 (mode 103 then: F_leg_ref carried)."""
+    ticks, res, _ = _force_family("nan_demand")
+    rows = FC.bad_rows(FC.BATCH, "nan_demand")[0]
+    hit = np.zeros(FC.BATCH, bool)
+    hit[rows] = True
+    carried = []
+    for t, r in enumerate(res):
+        assert np.all(r["status"] == FC.OK)
+        assert np.array_equal(r["qp_solution"] == 0, hit), t
+        assert np.array_equal(r["grf_opt"][hit], r["F_leg_guess"][hit], equal_nan=True)
+        assert np.all(np.isfinite(r["grf_opt"][~hit]))
+        hit = np.isnan(r["grf_opt"]).any(axis=1)  # what the next tick's g0 inherits
+        carried.append(int(hit.sum()))
+    assert carried == [12, 2, 1], carried
+
+
+def test_force_family_odd_flags_impose_no_rows():
+    """mode in {0, 100, 104} and right_support in {-1, 3} on tick 1: pattern
+    0 on all 64 (no swing-leg rows: every leg may carry force), all OK, and
+    F_leg_ref / F_leg_guess carried unchanged from tick 0 -- non-zero on the
+    robots that tick 0 ran in mode 101 or 102."""
+    ticks, res, _ = _force_family("odd_flags")
+    d = ticks[1][0]
+    assert set(d["mode"]) == {0, 100, 104} and set(d["right_support"]) == {-1, 3}
+    assert np.all(FC.pattern(d["mode"], d["right_support"]) == 0)
+    r = res[1]
+    assert np.all(r["status"] == FC.OK) and np.all(r["qp_solution"] == 1)
+    assert np.array_equal(r["F_leg_ref"], res[0]["F_leg_ref"]) and np.array_equal(r["F_leg_guess"], r["F_leg_ref"])
+    moved = np.isin(ticks[0][0]["mode"], (101, 102))
+    assert moved.sum() >= 32 and np.all(np.abs(r["F_leg_ref"][moved]).max(axis=1) > 1.0)
+    assert int(np.sum(r["iters"] >= 4)) >= 44  # measured 44 of 64
+
+
+def _body_family(name):
+    steps, run = BC.family(name)
+    act = np.array([i >= 100 for i, _ in steps])
+    g = lambda k: np.stack([r[k] for r in run.steps])
+    return steps, run, act, g
+
+
+def test_body_family_nan_reference_takes_the_fallback():
+    """NaN in zmp_ref(0, 0) on robots b % 4 == 0: 640 calls, all status OK;
+    qp_solution 0 and a NaN com_traj row on exactly those 160, the !ok branch
+    (body_mpc.c: thax0 = (thetaxk[0] - a0x) / b[0])."""
+    _, _, act, g = _body_family("nan_reference")
+    hit = (np.arange(BC.BATCH) % 4 == 0)[None, :] & act[:, None]
+    assert np.all(g("status") == BC.OK)
+    assert np.array_equal(g("qp_solution")[act] == 0, hit[act])
+    assert np.array_equal(np.isnan(g("com_traj")).any(axis=2), hit) and hit.sum() == 160
+
+
+def test_body_family_tilted_reference_reaches_the_bounds():
+    """angle_ref ~ N(0, 1 rad), 640 calls, all OK: an instrumented scratch
+    copy of the restatement counted more than one active-set iteration on
+    640 of 640 calls (up to 17) and the post-solve clamps (body_mpc.c: nx0 >
+    thetax_max ...) taken 2 / 2 / 4 / 0 times (x+, x-, y+, y-).  Visible in
+    the outputs: a predicted theta at +-10 deg on 428 rows, the first torque
+    at +-20 / j_ini on 380.  (Scales 0.05 and 0.1 rad reach no bound; 0.2 rad
+    reaches both, on half the calls.)"""
+    _, _, act, g = _body_family("tilted_reference")
+    assert np.all(g("status") == BC.OK) and np.all(g("qp_solution") == 1)
+    ct = g("com_traj")
+    assert np.all(np.isfinite(ct))
+    th = np.abs(ct[:, :, [0, 1, 6, 7, 10, 11]])
+    lim = 10 * np.pi / 180
+    assert th.max() <= lim + 1e-12
+    at_theta = int((np.abs(th - lim) <= 1e-12).any(axis=2).sum())
+    at_torque = int((np.abs(np.abs(ct[:, :, [2, 3]]) - 20 / 0.12) <= 1e-9).any(axis=2).sum())
+    print("tilted_reference: theta bound on %d rows, torque bound on %d" % (at_theta, at_torque))
+    assert at_theta >= 428 and at_torque >= 380
+
+
+def test_body_family_nan_accel_keeps_v_ini():
+    """NaN in comacc_ref(2, 1) on robots b % 4 == 1 at i = 110, 111, 125: G
+    holds pth^2 = (j_ini / (mass (acc_z + g)))^2, the Cholesky fails --
+    NOT_PD on those 12 calls, OK on the other 628 -- and, as in the reference
+    (PRMPCClass.cpp:803, :843-847), _V_ini keeps its (non-zero) value apart
+    from entries 0 and 4, which the post-processing rewrites; qp_solution 1.
+    com_traj is NaN in zmp_real(1) only (entries 8, 9)."""
+    steps, run, act, g = _body_family("nan_accel")
+    hit = np.zeros((len(steps), BC.BATCH), bool)
+    for k, (i, _) in enumerate(steps):
+        if i in BC.NAN_ACCEL_STEPS:
+            hit[k, np.arange(BC.BATCH) % 4 == 1] = True
+    assert hit.sum() == 12
+    assert np.array_equal(g("status"), np.where(hit, BC.NOT_PD, BC.OK))
+    assert np.all(g("qp_solution")[act] == 1)
+    keep = [1, 2, 3, 5, 6, 7]
+    vb, va = g("V_before")[hit], g("V_after")[hit]
+    assert va[:, keep].tobytes() == vb[:, keep].tobytes()
+    assert np.all(np.abs(vb[:, keep]).max(axis=1) > 0)
+    nan = np.isnan(g("com_traj"))
+    assert np.array_equal(nan.any(axis=2), hit) and not nan[:, :, [0, 1, 2, 3, 4, 5, 6, 7, 10, 11, 12, 13]].any()

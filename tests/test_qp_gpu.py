@@ -39,6 +39,13 @@ instrumented scratch copy of the restatement, not in the repository):
 
 No family reaches the degenerate-restore branch (add_constraint false after
 a full step: iaexcl, snapshot restore, goto l2); see DESIGN.md §4f.
+
+The kernels that run the same core inside a larger kernel (force_qp_kernel,
+body_mpc_kernel) are tested on the families of tests/force_cases.py and
+tests/body_cases.py -- legs at fz_max, active friction rows, failed
+factorisations (NOT_PD: grf_opt / _V_ini keep their values), NaN fallbacks,
+flags outside the gait table, bounds of the body QP; census in the tests'
+docstrings and in DESIGN.md §4.
 """
 import ctypes as C
 
@@ -49,6 +56,8 @@ torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
+import body_cases as BC  # noqa: E402
+import force_cases as FC  # noqa: E402
 import oracle_lib as O  # noqa: E402
 import qp_cases as Q  # noqa: E402
 from cases import force_inputs  # noqa: E402
@@ -141,7 +150,9 @@ def test_force_qp_matches_restatement_over_ticks(hw, grouped):
     instances and within 1e-9 otherwise -- with the sim's constants (mass 12,
     mu 0.25) and with the hardware copy's (unitree_legged_real: mass =
     gait::mass = 14, mu = 0.5, called at torque_mode.cpp:1364-1367), through
-    the plain and the grouped launch."""
+    the plain and the grouped launch.  Status, qp_solution and iterations
+    equal on every robot and tick.  These inputs (seed 7) all solve OK with
+    no leg at fz_max; the other kinds are test_force_qp_family_parity's."""
     dev = _dev()
     rng = np.random.default_rng(7)
     B, ticks = 96, 3
@@ -166,6 +177,7 @@ def test_force_qp_matches_restatement_over_ticks(hw, grouped):
         guess = out["F_leg_guess"].cpu().numpy()
         qps = out["qp_solution"].cpu().numpy()
         st = out["status"].cpu().numpy()
+        its = out["iters"].cpu().numpy()
         for b in range(B):
             d = lambda k, b=b: np.ascontiguousarray(inp[k][b], dtype=np.float64)
             O.lib().qo_force_distribution(C.byref(states[b]), O.P(d("com_des")), O.P(d("leg_des")),
@@ -183,6 +195,7 @@ def test_force_qp_matches_restatement_over_ticks(hw, grouped):
             ref = np.array(states[b].grf_opt[:])
             assert np.array_equal(guess[b], np.array(states[b].F_leg_guess[:])), b
             assert qps[b] == ok and st[b] == est.value, (b, qps[b], ok, st[b], est.value)
+            assert its[b] == eit.value, (tick, b, its[b], eit.value)
             assert np.allclose(g[b], ref, rtol=1e-9, atol=1e-8), (tick, b, g[b], ref)
             exact += int(np.array_equal(g[b], ref))
             total += 1
@@ -258,6 +271,22 @@ def test_force_qp_grouped_launch_replays_from_a_hip_graph():
         assert torch.equal(graphed.order_ws[:B], eager.order_ws[:B]), tick
 
 
+def _assert_grouping_state(solver, prev, inp, iters, what):
+    """The grouped solver's workspace after a call: order_ws[:B] carries this
+    call's iteration counts to the next, and order_ws[B:2B] -- the list the
+    call ran -- is a permutation of the robots in (pattern, min(previous
+    iterations, 15)) order; `prev` is order_ws[:B] from before the call."""
+    B = solver.batch
+    assert torch.equal(solver.order_ws[:B], iters), what  # carried for the next call
+    lst = solver.order_ws[B:2 * B].cpu().numpy()
+    assert np.array_equal(np.sort(lst), np.arange(B)), what
+    m, rs = inp["mode"][lst], inp["right_support"][lst]
+    pat = np.where(m == 102, np.where(rs == 0, 1, np.where(rs == 1, 2, 0)),
+                   np.where(m == 101, np.where(rs == 0, 3, np.where(rs == 1, 4, 0)), 0))
+    key = pat * 16 + np.minimum(prev.cpu().numpy()[lst], 15)
+    assert np.all(np.diff(key) >= 0), what
+
+
 def test_force_qp_grouped_launch_is_bit_identical():
     """qloco_force_qp_solve_ordered groups the robots by swing-leg pattern and
     previous iteration count before the launch; every robot's
@@ -281,14 +310,154 @@ def test_force_qp_grouped_launch_is_bit_identical():
         torch.cuda.synchronize()
         for k in ("grf_opt", "F_leg_guess", "F_leg_ref", "qp_solution", "status", "iters"):
             assert torch.equal(og[k], op[k]), (tick, k)
-        assert torch.equal(grouped.order_ws[:B], op["iters"]), tick  # carried for the next call
-        lst = grouped.order_ws[B:2 * B].cpu().numpy()
-        assert np.array_equal(np.sort(lst), np.arange(B)), tick
-        m, rs = inp["mode"][lst], inp["right_support"][lst]
-        pat = np.where(m == 102, np.where(rs == 0, 1, np.where(rs == 1, 2, 0)),
-                       np.where(m == 101, np.where(rs == 0, 3, np.where(rs == 1, 4, 0)), 0))
-        key = pat * 16 + np.minimum(prev.cpu().numpy()[lst], 15)
-        assert np.all(np.diff(key) >= 0), tick
+        _assert_grouping_state(grouped, prev, inp, op["iters"], tick)
+
+
+# ---- the force block on the families of tests/force_cases.py ----------------
+
+FORCE_OUT = ("grf_opt", "F_leg_guess", "F_leg_ref", "qp_solution", "status", "iters")
+FORCE_LAUNCHES = [(False, 8), (True, 8), (False, 16), (True, 16)]  # (grouped, group width)
+
+
+def _force_dev(d, dev):
+    return {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in d.items()}
+
+
+def _force_set_params(solver, over):
+    """The tick's constants: the solver's own (sim or hardware copy) with the
+    family's overrides (alpha, beta, gamma) -- equal to the restatement's."""
+    prm = FC.oracle_params(**over)
+    for k in ("alpha", "beta", "gamma", "fz_max"):
+        setattr(solver.params, k, getattr(prm, k))
+    assert (solver.params.mass, solver.params.mu) == (prm.mass, prm.mu)
+
+
+def _force_step(solver, d, dev):
+    out = solver.step(**_force_dev(d, dev))
+    torch.cuda.synchronize()
+    return {k: out[k].cpu().numpy() for k in FORCE_OUT}
+
+
+class _group_width:
+    def __init__(self, gw):
+        self.gw = gw
+
+    def __enter__(self):
+        from quadrupedal_loco_amd._lib import lib
+        self.prev = lib().qloco_force_set_group_width(self.gw)
+        assert self.prev in (8, 16)
+
+    def __exit__(self, *exc):
+        from quadrupedal_loco_amd._lib import lib
+        lib().qloco_force_set_group_width(self.prev)
+
+
+@pytest.mark.parametrize("grouped,gw", FORCE_LAUNCHES)
+@pytest.mark.parametrize("name", FC.FAMILIES)
+def test_force_qp_family_parity(name, grouped, gw):
+    """qp.ForceQP on every family of tests/force_cases.py (B = 64, two or
+    three ticks, member state carried) against the restatement, through the
+    plain and the grouped launch at both group widths.  The census the CPU
+    tests assert on the restatement (tests/test_oracle.py, seed 3):
+      baseline      all OK; double support at >= 4 iterations on 12 / 26 robots
+      heavy         all OK; a leg at fz_max on 47 / 55; 1-5 iterations
+      lateral       all OK; friction rows active on 64 / 64; up to 9 iterations
+      bad_position  tick 1: NOT_PD, 0 iterations on 32 (16 NaN, 16 +Inf), 32 OK
+      zero_weights  tick 1: NOT_PD on 64
+      alpha0        all OK; closed form on 43 / 30 robots, restatement 1.42e-14 N
+      nan_demand    tick 0: qp_solution 0 on 16, NaN grf_opt on 12; 12 / 2 stay
+      odd_flags     tick 1: pattern 0 on 64, F_leg_ref carried, all OK
+      hw_heavy / hw_lateral   as heavy / lateral with mass 14, mu 0.5
+    Per robot and tick: F_leg_guess, F_leg_ref, qp_solution, status and
+    iterations equal (NaN by position); grf_opt within 1e-9 relative / 1e-8 N,
+    equal by position on the fallback rows, and bit-identical on >= 90 % of
+    this family's solved robots.  On NOT_PD robots grf_opt is bit-equal to its
+    value before the call (the definition in include/qloco.h); a healthy batch
+    of the same size is launched just before every such tick, so the LDS the
+    failing groups find is other robots' data and not zeros.  alpha0: the
+    kernel within 16 x the restatement's own error of the closed form.
+    Grouped: the workspace's list stays a permutation in class order, also on
+    the tick after the NOT_PD robots left 0 iterations in it."""
+    dev = _dev()
+    ticks, run = FC.family(name)
+    B = FC.BATCH
+    hw = name.startswith("hw_")
+    solver = qp.ForceQP(batch=B, device=dev, grouped=grouped, hw=hw)
+    primer = qp.ForceQP(batch=B, device=dev, grouped=grouped)
+    prime_in = _force_dev(FC.ticks_of("heavy", B=B)[0][0], dev)
+    exact = solved = 0
+    with _group_width(gw):
+        for t, ((d, over), r) in enumerate(zip(ticks, run.ticks)):
+            _force_set_params(solver, over)
+            before = solver.grf_opt.cpu().numpy().copy()
+            prev = solver.order_ws[:B].clone() if grouped else None
+            bad = r["status"] == FC.NOT_PD
+            if bad.any():
+                primer.step(**prime_in)
+            g = _force_step(solver, d, dev)
+            what = (name, grouped, gw, t)
+            for k in ("F_leg_guess", "F_leg_ref"):
+                assert np.array_equal(g[k], r[k], equal_nan=True), (what, k)
+            for k in ("qp_solution", "status", "iters"):
+                assert np.array_equal(g[k], r[k]), (what, k, g[k], r[k])
+            fb =r["qp_solution"] == 0
+            assert np.array_equal(g["grf_opt"][fb], r["grf_opt"][fb], equal_nan=True), what
+            assert np.array_equal(np.isnan(g["grf_opt"]), np.isnan(r["grf_opt"])), what
+            assert np.allclose(g["grf_opt"][~fb], r["grf_opt"][~fb], rtol=1e-9, atol=1e-8), what
+            assert g["grf_opt"][bad].tobytes() == before[bad].tobytes(), (what, g["grf_opt"][bad], before[bad])
+            if bad.any():
+                assert np.all(np.abs(before[bad]).max(axis=1) > 1.0), what
+            ok = (r["status"] == FC.OK) & ~fb
+            exact += int(np.sum(np.all(g["grf_opt"][ok] == r["grf_opt"][ok], axis=1)))
+            solved += int(ok.sum())
+            if name == "alpha0":
+                x, rows = FC.alpha0_closed_form(d, over, r)
+                err_ref = np.abs(r["grf_opt"][rows] - x[rows]).max()
+                err = np.abs(g["grf_opt"][rows] - x[rows]).max()
+                print("alpha0 tick %d: %d robots, |grf - closed form| %.3g (restatement %.3g, bound %.3g)" % (
+                    t, len(rows), err, err_ref, 16 * err_ref))
+                assert len(rows) >= 30 and err <= 16 * err_ref, (what, err, err_ref)
+            if grouped:
+                _assert_grouping_state(solver, prev, d, solver.iters, what)
+    print("%s grouped=%s gw=%d: grf_opt bit-identical on %d of %d solved" % (name, grouped, gw, exact, solved))
+    assert solved >= 64 and exact >= 0.9 * solved, (name, exact, solved)
+
+
+@pytest.mark.parametrize("grouped,gw", FORCE_LAUNCHES)
+def test_force_qp_bad_robots_do_not_disturb_their_neighbours(grouped, gw):
+    """B = 67 `heavy` robots over three ticks; on ticks 1 and 2 the robots at
+    positions 0, 7, 8 and 66 -- a group boundary of a wave at both widths and
+    the partial last block -- get a NaN base_p[0], a NaN demand, a +Inf
+    base_p[0] and a NaN demand.  The bad robots end NOT_PD with grf_opt kept
+    (0, 8) or in the F_leg_guess fallback (7, 66); every other robot's outputs
+    equal, bit for bit, those of the same batch with the four left healthy."""
+    dev = _dev()
+    B = 67
+    ticks = FC.ticks_of("heavy", B=B, ticks=3)
+    poisoned = []
+    for t, (d, over) in enumerate(ticks):
+        d = {k: v.copy() for k, v in d.items()}
+        if t >= 1:
+            FC.bad_position(d, rows_nan=[0], rows_inf=[8])
+            FC.nan_demand(d, rows=[7, 66])
+        poisoned.append((d, over))
+    healthy = np.setdiff1d(np.arange(B), [0, 7, 8, 66])
+    a = qp.ForceQP(batch=B, device=dev, grouped=grouped)
+    b = qp.ForceQP(batch=B, device=dev, grouped=grouped)
+    with _group_width(gw):
+        for t in range(3):
+            before = b.grf_opt.cpu().numpy().copy()
+            ga = _force_step(a, ticks[t][0], dev)
+            gb = _force_step(b, poisoned[t][0], dev)
+            for k in FORCE_OUT:
+                assert ga[k][healthy].tobytes() == gb[k][healthy].tobytes(), (grouped, gw, t, k)
+            assert np.all(ga["status"] == FC.OK) and np.all(ga["qp_solution"] == 1)
+            if t >= 1:
+                assert gb["status"][[0, 8]].tolist() == [FC.NOT_PD, FC.NOT_PD] and np.all(gb["iters"][[0, 8]] == 0)
+                assert gb["grf_opt"][[0, 8]].tobytes() == before[[0, 8]].tobytes()
+                assert np.all(np.abs(before[[0, 8]]).max(axis=1) > 1.0)
+                assert np.all(gb["qp_solution"][[7, 66]] == 0)
+                assert np.array_equal(gb["grf_opt"][[7, 66]], gb["F_leg_guess"][[7, 66]], equal_nan=True)
 
 
 def test_hw_torque_ff_bit_exact():
@@ -339,6 +508,7 @@ def test_body_mpc_matches_restatement_over_a_gait():
         out = solver.step(**{k: torch.from_numpy(v).to(dev) for k, v in ins.items()})
         torch.cuda.synchronize()
         traj = out["com_traj"].cpu().numpy()
+        status = out["status"].cpu().numpy()
         state = solver.state.cpu().numpy()
         for b in range(B):
             ct = np.zeros(14)
@@ -349,12 +519,62 @@ def test_body_mpc_matches_restatement_over_a_gait():
                                       O.P(ins["comacc_ref"][b].copy()), O.P(np.zeros(9)), O.P(ct),
                                       C.byref(est))
             assert np.allclose(traj[b], ct, rtol=1e-9, atol=1e-12), (i, b, traj[b], ct)
+            assert status[b] == est.value, (i, b, status[b], est.value)
             if i >= 100:
                 o = ostates[b]
                 assert (int(state[b, 26]), int(state[b, 27]), int(state[b, 28])) == \
                     (o.bjx1, o.bjx2, o.t_yu), (i, b)
     for s in ostates:
         O.lib().qo_body_free(C.byref(s))
+
+
+@pytest.mark.parametrize("name", BC.FAMILIES)
+def test_body_mpc_family_parity(name):
+    """qp.BodyMPC on the families of tests/body_cases.py (B = 16, i = 96 ..
+    139: 640 acting calls) against the restatement; the census the CPU tests
+    assert (tests/test_oracle.py):
+      nan_reference     all OK; the !ok fallback and a NaN com_traj row on 160
+      tilted_reference  all OK; more than one active-set iteration on 640 of
+                        640 calls (up to 17), the post-solve clamps taken 8
+                        times (counted in an instrumented scratch copy of the
+                        restatement); a theta at its bound on 428 rows, the
+                        torque on 380
+      nan_accel         NOT_PD on 12 calls (G holds the NaN), OK on 628
+    Every call: status equal, com_traj NaN in the same positions and within
+    1e-9 relative / 1e-12 elsewhere, the carried _V_ini likewise, the
+    schedule integers equal.  On NOT_PD calls _V_ini entries 1-3 and 5-7
+    (0 and 4 are rewritten after the solve) are bit-equal to their values
+    before the call -- non-zero, and a batch of other robots is launched just
+    before, so the LDS the failing groups find is not zeros."""
+    dev = _dev()
+    steps, run = BC.family(name)
+    B = BC.BATCH
+    solver = qp.BodyMPC(batch=B, device=dev)
+    primer = qp.BodyMPC(batch=B, device=dev)
+    prime_in = {k: torch.from_numpy(v).to(dev) for k, v in BC.steps_of("tilted_reference", steps=(120,))[0][1].items()}
+    keep = [5, 6, 7, 9, 10, 11]  # state columns of _V_ini entries 1-3, 5-7
+    for (i, ins), r in zip(steps, run.steps):
+        before = solver.state.cpu().numpy().copy()
+        bad = r["status"] == BC.NOT_PD
+        if bad.any():
+            primer.step(**prime_in)
+        out = solver.step(**{k: torch.from_numpy(v).to(dev) for k, v in ins.items()})
+        torch.cuda.synchronize()
+        traj, status = out["com_traj"].cpu().numpy(), out["status"].cpu().numpy()
+        state = solver.state.cpu().numpy()
+        assert np.array_equal(status, r["status"]), (name, i, status, r["status"])
+        assert np.array_equal(np.isnan(traj), np.isnan(r["com_traj"])), (name, i)
+        assert np.allclose(traj, r["com_traj"], rtol=1e-9, atol=1e-12, equal_nan=True), (name, i)
+        if i >= 100:
+            assert np.array_equal(state[:, 26:29].astype(np.int32), r["sched"]), (name, i)
+            assert np.array_equal(state[:, 29].astype(np.int32), r["qp_solution"]), (name, i)
+            assert np.array_equal(np.isnan(state[:, 4:12]), np.isnan(r["V_after"])), (name, i)
+            # angular accelerations, up to 1389 rad/s^2; theta = .. + 5e-5 V, so
+            # com_traj's 1e-12 absolute is 2e-8 here: 1e-9 is the tighter one
+            assert np.allclose(state[:, 4:12], r["V_after"], rtol=1e-9, atol=1e-9, equal_nan=True), (name, i)
+        assert state[bad][:, keep].tobytes() == before[bad][:, keep].tobytes(), (name, i)
+        if bad.any():
+            assert np.all(np.abs(before[bad][:, keep]).max(axis=1) > 0), (name, i)
 
 
 def test_indexfind_bit_exact():

@@ -43,10 +43,14 @@ def test_oracle_under_asan_ubsan(tmp_path):
             g, c = synth_messages(20261016, B, t)
             np.ascontiguousarray(g, np.float64).tofile(f)
             np.ascontiguousarray(c, np.float64).tofile(f)
-    d = force_inputs(np.random.default_rng(3), 64)
+    # 64 healthy robots, then two with a bad base position (force_cases.py
+    # bad_position: NaN, +Inf); the driver carries one Dynamiccclass through
+    # them all, so the failed factorisations meet a non-zero grf_opt
+    d = {k: np.array(v) for k, v in force_inputs(np.random.default_rng(3), 66).items()}
+    d["base_p"][64, 0], d["base_p"][65, 0] = np.nan, np.inf
     with open(tmp_path / "force.bin", "wb") as f:
-        np.array([64], np.int32).tofile(f)
-        for b in range(64):
+        np.array([66], np.int32).tofile(f)
+        for b in range(66):
             rec = np.zeros(52)
             rec[0:3], rec[3:15], rec[15:21] = d["com_des"][b], d["leg_des"][b], d["F_force_des"][b]
             rec[21:24], rec[24:27], rec[27:30] = d["rfoot_des"][b], d["lfoot_des"][b], d["base_p"][b]
@@ -59,6 +63,7 @@ def test_oracle_under_asan_ubsan(tmp_path):
     assert r.returncode == 0, out[-4000:]
     assert "runtime error" not in out and "AddressSanitizer" not in out, out[-4000:]
     assert "rt %d" % (T * B) in r.stdout
+    assert "force_qp %d (not_pd 6)" % (3 * 66) in r.stdout, r.stdout
     del O
 
 

@@ -44,6 +44,52 @@ def test_servo_block_matches_oracle_over_ticks():
     assert exact >= 0.9 * total, (exact, total)
 
 
+def test_servo_block_heavy_demand_and_bad_position():
+    """The force kernel's second caller on the `heavy` and `bad_position`
+    inputs of tests/force_cases.py, three ticks, B = 96: coma_des z + 3 g on
+    every tick (F_sum z = 4 m g: legs at fz_max), and on tick 1 body_p_des x
+    NaN on robots b % 4 == 1, +Inf on b % 4 == 3.  Those 48 end NOT_PD with
+    grf_opt bit-equal to tick 0's (non-zero), qp_solution 1 -- the rule of
+    include/qloco.h -- and solve again on tick 2; the existing assertions
+    hold throughout (tau NaN in the same positions: a NaN body position
+    reaches the swing-leg torques)."""
+    dev = _dev()
+    B, T = 96, 3
+    blk = ServoForceBlock(B, dev)
+    orc = O.ServoOracle(B)
+    b = np.arange(B)
+    bad = (b % 4 == 1) | (b % 4 == 3)
+    exact = total = 0
+    last = None
+    for t in range(T):
+        d = synth_servo_inputs(7, B, t)
+        d["coma_des"] = d["coma_des"] + np.array([0.0, 0.0, 3 * 9.8])
+        if t == 1:
+            d["body_p_des"] = d["body_p_des"].copy()
+            d["body_p_des"][b % 4 == 1, 0] = np.nan
+            d["body_p_des"][b % 4 == 3, 0] = np.inf
+        o = blk.step(**{k: torch.from_numpy(np.ascontiguousarray(v)).to(dev) for k, v in d.items()})
+        g = {k: v.cpu().numpy() for k, v in o.items()}
+        r = orc.step(d)
+        for k in ("F_sum", "Force_L_R", "swing", "qp_solution", "status"):
+            assert np.array_equal(g[k], r[k]), (t, k)
+        assert np.allclose(g["grf_opt"], r["grf_opt"], rtol=1e-9, atol=1e-8), t
+        assert np.array_equal(np.isnan(g["tau"]), np.isnan(r["tau"])), t
+        assert np.allclose(g["tau"], r["tau"], rtol=1e-9, atol=1e-9, equal_nan=True), t
+        if t == 1:
+            assert np.array_equal(r["status"], np.where(bad, 5, 0)) and np.all(r["qp_solution"] == 1)
+            assert g["grf_opt"][bad].tobytes() == last[bad].tobytes()
+            assert np.all(np.abs(last[bad]).max(axis=1) > 1.0)
+        else:
+            assert np.all(r["status"] == 0) and np.all(np.isfinite(g["grf_opt"]))
+            assert int(np.sum(np.abs(g["grf_opt"].reshape(B, 4, 3)[:, :, 2] - 160.0).min(axis=1) <= 1e-7)) >= B // 2
+        sel = r["status"] == 0
+        exact += int(np.sum(np.all(g["grf_opt"][sel] == r["grf_opt"][sel], axis=1)))
+        total += int(sel.sum())
+        last = g["grf_opt"].copy()
+    assert exact >= 0.9 * total, (exact, total)
+
+
 def test_servo_block_rejects_bad_args():
     from quadrupedal_loco_amd._lib import ForceParams, lib
     import ctypes as C
