@@ -19,32 +19,21 @@
 // wave stages 16 rows at a time through LDS and writes them coalesced.
 //
 // The 7 x 7 system of CoM_height_solve is solved again for the tail: its
-// coefficients are not an output of section 15.  nd_powers / nd_lu /
-// nd_lu_solve are copies of the tk_ functions of qloco_nlp_tick.hip.
+// coefficients are not an output of section 15.  The powers, the LU, the fill
+// of AAA (the host's too, for the squat polynomial), the polynomial and the
+// three records' layouts are those of qloco_nlp_core.hpp, which the tick
+// kernel includes as well; the block that puts them together keeps the order
+// this kernel was tuned in (profiles/nlp_core_ab.txt).
 #include <atomic>
 #include <cmath>
 #include <cstdlib>
 
-#include "qloco_common.hpp"
+#include "qloco_nlp_core.hpp"
 
 namespace qloco {
 
-constexpr int ND_NS = QLOCO_NLP_STEPS;
-constexpr int ND_RING = QLOCO_NLP_NODE_RING;
-constexpr int ND_REC = QLOCO_NLP_NODE_STATE;
-constexpr int ND_SCR = QLOCO_NLP_NODE_SCRATCH;
-constexpr int ND_ROWLEN = QLOCO_GAIT_MSG_LEN;
 constexpr int ND_TAIL = 9;  // largest _nTdx
 constexpr int ND_TILE = 16; // rows per LDS pass
-constexpr int64_t kNodeMaxBatch = (int64_t)1 << 24;
-enum { N_COUNT = 0, N_LATCH = 1, N_RESTART = 2, N_STOP = 3, N_COL = 4, N_COR = 7, N_RINGF = 10, N_ROW = 154 };
-static_assert(N_RINGF + ND_RING * 3 == N_ROW && N_ROW + ND_ROWLEN == ND_REC, "record length");
-// scratch, doubles per robot from the end of the records
-enum { S_CT = 0, S_RL = 38, S_COM = 56, S_VARI = 74, S_EST = 78, S_RF = 84, S_LF = 86, S_PREV = 88, S_INT = 90 };
-static_assert(S_INT + 4 == ND_SCR, "scratch length");
-// fields of the section-14 record past ts / tx (qloco_nlp.hip) and of section 15's (qloco_nlp_tick.hip)
-enum { F_TD = 0, F_FX = 81, F_FY = 108, F_CXI = 135, F_CVXI = 162, F_CYI = 189, F_CVYI = 216 };
-enum { T_BJX1 = 0, T_SW0 = 3, T_FZ = 5, T_TX0 = 59 };
 
 struct NodeArgs {
   qloco_nlp_params prm;
@@ -70,136 +59,21 @@ struct NodeScratch {
 __host__ __device__ __forceinline__ NodeScratch node_scratch(double *ws, int64_t B) {
   double *const s = ws + (int64_t)ND_REC * B;
   NodeScratch o;
-  o.ct = s + (int64_t)S_CT * B;
-  o.rl = s + (int64_t)S_RL * B;
-  o.com = s + (int64_t)S_COM * B;
-  o.vari = s + (int64_t)S_VARI * B;
-  o.est = s + (int64_t)S_EST * B;
-  o.rf = s + (int64_t)S_RF * B;
-  o.lf = s + (int64_t)S_LF * B;
-  o.prev = s + (int64_t)S_PREV * B;
-  int32_t *const n = (int32_t *)(s + (int64_t)S_INT * B);
+  o.ct = s + (int64_t)NS_CT * B;
+  o.rl = s + (int64_t)NS_RL * B;
+  o.com = s + (int64_t)NS_COM * B;
+  o.vari = s + (int64_t)NS_VARI * B;
+  o.est = s + (int64_t)NS_EST * B;
+  o.rf = s + (int64_t)NS_RF * B;
+  o.lf = s + (int64_t)NS_LF * B;
+  o.prev = s + (int64_t)NS_PREV * B;
+  int32_t *const n = (int32_t *)(s + (int64_t)NS_INT * B);
   o.t_int = n;
   o.rs = n + B;
   o.sched = n + 2 * B;
   o.st = n + 6 * B;
   o.branch = n + 7 * B;
   return o;
-}
-
-__device__ __forceinline__ int nd_int(double v) { return (v > -1.0e9 && v < 1.0e9) ? (int)v : -1; }
-
-__device__ __forceinline__ double nd_at(const double *p, int64_t stride, int k) {
-  return (k >= 0 && k < ND_NS) ? p[(int64_t)k * stride] : __builtin_nan("");
-}
-
-// t^2 .. t^6 as pow() returns them (qloco_nlp_tick.hip)
-__device__ __forceinline__ void nd_powers(double t, double (&p)[7]) {
-  p[0] = 1.0;
-  p[1] = t;
-  double h = t * t, l = __builtin_fma(t, t, -h);
-  p[2] = h;
-#pragma unroll
-  for (int n = 3; n <= 6; ++n) {
-    const double q = h * t;
-    const double e = __builtin_fma(h, t, -q) + l * t;
-    h = q + e;
-    l = e - (h - q);
-    p[n] = h;
-  }
-}
-
-// partial-pivot LU with the right-hand sides carried along, then the
-// substitutions (qloco_nlp_tick.hip); also the host's, for the squat polynomial
-template <int N, int M>
-__host__ __device__ __forceinline__ void nd_lu(double (&a)[N][N], double (&r)[N][M]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    int p = k;
-    double best = fabs(a[k][k]);
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      const double v = fabs(a[q][k]);
-      const bool g = v > best;
-      p = g ? q : p;
-      best = g ? v : best;
-    }
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      const bool s = p == q;
-#pragma unroll
-      for (int c = 0; c < N; ++c) {
-        const double x = a[k][c], y = a[q][c];
-        a[k][c] = s ? y : x;
-        a[q][c] = s ? x : y;
-      }
-#pragma unroll
-      for (int c = 0; c < M; ++c) {
-        const double x = r[k][c], y = r[q][c];
-        r[k][c] = s ? y : x;
-        r[q][c] = s ? x : y;
-      }
-    }
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      a[q][k] = a[q][k] / a[k][k];
-#pragma unroll
-      for (int c = k + 1; c < N; ++c) a[q][c] = a[q][c] - a[q][k] * a[k][c];
-    }
-  }
-}
-
-template <int N, int M>
-__host__ __device__ __forceinline__ void nd_lu_solve(const double (&a)[N][N], double (&r)[N][M]) {
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      double acc = r[q][m];
-#pragma unroll
-      for (int c = 0; c < q; ++c) acc = acc - a[q][c] * r[c][m];
-      r[q][m] = acc;
-    }
-#pragma unroll
-    for (int q = N - 1; q >= 0; --q) {
-      double acc = r[q][m];
-#pragma unroll
-      for (int c = q + 1; c < N; ++c) acc = acc - a[q][c] * r[c][m];
-      r[q][m] = acc / a[q][q];
-    }
-  }
-}
-
-// rows of AAA (:2386-2412, :3599-3625) from the powers of the three plan times;
-// columns 2, 3, 4 of the identity as right-hand sides
-__host__ __device__ __forceinline__ void nd_fill(const double (&pw)[3][7], double (&m)[7][7], double (&r)[7][3]) {
-  constexpr int kind[7] = {1, 2, 0, 0, 0, 1, 2}, which[7] = {0, 0, 0, 1, 2, 2, 2};
-#pragma unroll
-  for (int q = 0; q < 7; ++q) {
-    const double *const p = pw[which[q]];
-    const double t = p[1], t2 = p[2], t3 = p[3], t4 = p[4], t5 = p[5], t6 = p[6];
-    if (kind[q] == 0) {
-      m[q][0] = t6; m[q][1] = t5; m[q][2] = t4; m[q][3] = t3; m[q][4] = t2; m[q][5] = t; m[q][6] = 1.0;
-    } else if (kind[q] == 1) {
-      m[q][0] = 6 * t5; m[q][1] = 5 * t4; m[q][2] = 4 * t3; m[q][3] = 3 * t2; m[q][4] = 2 * t; m[q][5] = 1.0; m[q][6] = 0.0;
-    } else {
-      m[q][0] = 30 * t4; m[q][1] = 20 * t3; m[q][2] = 12 * t2; m[q][3] = 6 * t; m[q][4] = 2.0; m[q][5] = 0.0; m[q][6] = 0.0;
-    }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) r[q][c] = (q == c + 2) ? 1.0 : 0.0;
-  }
-}
-
-// position, velocity and acceleration rows times the coefficients, in Eigen's order
-__device__ __forceinline__ void nd_poly(double t, const double (&co)[7], double &z, double &vz, double &az) {
-  double pw[7];
-  nd_powers(t, pw);
-  const double t2 = pw[2], t3 = pw[3], t4 = pw[4], t5 = pw[5], t6 = pw[6];
-  z = (((((t6 * co[0] + t5 * co[1]) + t4 * co[2]) + t3 * co[3]) + t2 * co[4]) + t * co[5]) + 1.0 * co[6];
-  vz = ((((((6 * t5) * co[0] + (5 * t4) * co[1]) + (4 * t3) * co[2]) + (3 * t2) * co[3]) + (2 * t) * co[4]) +
-        1.0 * co[5]) + 0.0 * co[6];
-  az = ((((((30 * t4) * co[0] + (20 * t3) * co[1]) + (12 * t2) * co[2]) + (6 * t) * co[3]) + 2.0 * co[4]) +
-        0.0 * co[5]) + 0.0 * co[6];
 }
 
 // _zmpx_real / _zmpy_real at array index k
@@ -209,10 +83,10 @@ __device__ __forceinline__ void nd_ring_rd(const double *w, int64_t B, int k, do
     return;
   }
   const int s = k % ND_RING;
-  const double tag = w[(int64_t)(N_RINGF + 3 * s) * B];
+  const double tag = w[(int64_t)(ND_RINGF + 3 * s) * B];
   if (tag == (double)k) {
-    x = w[(int64_t)(N_RINGF + 3 * s + 1) * B];
-    y = w[(int64_t)(N_RINGF + 3 * s + 2) * B];
+    x = w[(int64_t)(ND_RINGF + 3 * s + 1) * B];
+    y = w[(int64_t)(ND_RINGF + 3 * s + 2) * B];
   } else if (tag > (double)k) {  // a later index has taken the entry
     x = y = __builtin_nan("");
   } else {  // never written (:526)
@@ -222,9 +96,9 @@ __device__ __forceinline__ void nd_ring_rd(const double *w, int64_t B, int k, do
 
 __device__ __forceinline__ void nd_ring_wr(double *w, int64_t B, int k, double x, double y) {
   const int s = k % ND_RING;  // k >= 1
-  w[(int64_t)(N_RINGF + 3 * s) * B] = (double)k;
-  w[(int64_t)(N_RINGF + 3 * s + 1) * B] = x;
-  w[(int64_t)(N_RINGF + 3 * s + 2) * B] = y;
+  w[(int64_t)(ND_RINGF + 3 * s) * B] = (double)k;
+  w[(int64_t)(ND_RINGF + 3 * s + 1) * B] = x;
+  w[(int64_t)(ND_RINGF + 3 * s + 2) * B] = y;
 }
 
 // a diagonal 3 x 3 times a vector as Eigen sums the full row
@@ -248,25 +122,25 @@ __global__ __launch_bounds__(256) void nlp_node_pre_kernel(const NodeArgs a) {
   double *const w = a.ws + rb;
   const NodeScratch s = node_scratch(a.ws, B);
   const double *const msg = a.nrt + (int64_t)QLOCO_NRT_MSG_LEN * rb;
-  double count = w[(int64_t)N_COUNT * B];
-  bool latch = w[(int64_t)N_LATCH * B] != 0.0;
+  double count = w[(int64_t)ND_COUNT * B];
+  bool latch = w[(int64_t)ND_LATCH * B] != 0.0;
   if (msg[0] > 0) {  // gait_nlp_kmp.cpp:106-110
     latch = true;
     count = count + 1;
-    w[(int64_t)N_COUNT * B] = count;
-    w[(int64_t)N_LATCH * B] = 1.0;
+    w[(int64_t)ND_COUNT * B] = count;
+    w[(int64_t)ND_LATCH * B] = 1.0;
   }
   int branch, w1 = 0, ti = 0;
-  if (!(w[(int64_t)N_STOP * B] < 1)) {  // :120
+  if (!(w[(int64_t)ND_STOP * B] < 1)) {  // :120
     branch = QLOCO_NLP_NODE_STOPPED;
   } else {
-    w1 = nd_int(count) - nd_int(w[(int64_t)N_RESTART * B]);  // NLPRTControlClass.cpp:196
+    w1 = nlp_int(count) - nlp_int(w[(int64_t)ND_RESTART * B]);  // NLPRTControlClass.cpp:196
     if (!latch) {
       branch = QLOCO_NLP_NODE_NOT_STARTED;
     } else if (w1 * a.np.dtx <= a.np.height_offset_time) {  // :207
       branch = QLOCO_NLP_NODE_SQUAT;
     } else {
-      w1 = nd_int((double)w1 - a.wsub);  // :246, an int -= double
+      w1 = nlp_int((double)w1 - a.wsub);  // :246, an int -= double
       if (w1 < a.wmax) {                 // :247; rt_nlp_gait ticks for _t_int >= 1 (:439)
         branch = QLOCO_NLP_NODE_WALKING;
         ti = w1 >= 1 ? w1 : 0;
@@ -284,11 +158,11 @@ __global__ __launch_bounds__(256) void nlp_node_pre_kernel(const NodeArgs a) {
   s.rf[2 * rb + 0] = msg[22];
   s.rf[2 * rb + 1] = msg[23];
   // what the tick overwrites and the tail needs: _bjx1 (:936) and _td(1) (:933)
-  s.prev[2 * rb + 0] = a.tws[(int64_t)T_BJX1 * B + rb];
-  s.prev[2 * rb + 1] = a.nws[2 * B * ND_NS + (int64_t)(F_TD + 1) * B + rb];
+  s.prev[2 * rb + 0] = a.tws[(int64_t)TK_BJX1 * B + rb];
+  s.prev[2 * rb + 1] = a.nws[2 * B * NLP_NS + (int64_t)(ST_TD + 1) * B + rb];
   if (a.sched) {
     a.sched[QLOCO_NLP_NODE_SCHED_LEN * rb + 1] = w1;
-    a.sched[QLOCO_NLP_NODE_SCHED_LEN * rb + 5] = nd_int(count);
+    a.sched[QLOCO_NLP_NODE_SCHED_LEN * rb + 5] = nlp_int(count);
   }
 }
 
@@ -296,7 +170,7 @@ __global__ __launch_bounds__(256) void nlp_node_pre_kernel(const NodeArgs a) {
 __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
   const int64_t B = a.batch;
   double *const w = a.ws + rb;
-  double *const row = w + (int64_t)N_ROW * B;  // slot k at row[k * B]
+  double *const row = w + (int64_t)ND_ROW * B;  // slot k at row[k * B]
   const NodeScratch s = node_scratch(a.ws, B);
   const int branch = s.branch[rb];
   const double hw = a.prm.half_hip_width, mass = a.np.totalmass;
@@ -304,10 +178,10 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
 #define ROW(k) row[(int64_t)(k) * B]
   if (branch == QLOCO_NLP_NODE_NOT_STARTED || branch == QLOCO_NLP_NODE_SQUAT) {
     if (branch == QLOCO_NLP_NODE_SQUAT) {  // NLPRTControlClass.cpp:209-242
-      const int w1 = nd_int(w[(int64_t)N_COUNT * B]) - nd_int(w[(int64_t)N_RESTART * B]);
+      const int w1 = nlp_int(w[(int64_t)ND_COUNT * B]) - nlp_int(w[(int64_t)ND_RESTART * B]);
       const double t_des = w1 * a.np.dtx;
       double z = a.prm.z_c - a.np.height_offset, vz = 0.0, az = 0.0;
-      if (t_des <= a.np.height_squat_time) nd_poly(t_des, a.sq, z, vz, az);
+      if (t_des <= a.np.height_squat_time) nlp_poly(t_des, a.sq, z, vz, az);
       ROW(0) = 0.0;
       ROW(1) = 0.0;
       ROW(2) = z;
@@ -345,8 +219,8 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
   } else if (branch == QLOCO_NLP_NODE_OVER_TIME) {  // :256-259
     ROW(99) = 2.0;
     ROW(97) = 2.0;
-    w[(int64_t)N_STOP * B] = 2.0;
-    w[(int64_t)N_RESTART * B] = w[(int64_t)N_COUNT * B];
+    w[(int64_t)ND_STOP * B] = 2.0;
+    w[(int64_t)ND_RESTART * B] = w[(int64_t)ND_COUNT * B];
   } else if (branch == QLOCO_NLP_NODE_WALKING) {
     const int sst = s.st[rb];
     status = sst;
@@ -357,15 +231,15 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
       const double *const ct = s.ct + 38 * rb, *const rl = s.rl + 18 * rb;
       const int period = s.sched[4 * rb + 0], bjx1 = s.sched[4 * rb + 3];
       const int pi = period - 1;
-      const double *const ts = a.nws + rb * ND_NS;
-      const double *const tx = a.nws + B * ND_NS + rb * ND_NS;
-      const double *const fm = a.nws + 2 * B * ND_NS + rb;
+      const double *const ts = a.nws + rb * NLP_NS;
+      const double *const tx = a.nws + B * NLP_NS + rb * NLP_NS;
+      const double *const fm = a.nws + 2 * B * NLP_NS + rb;
       const double *const tw = a.tws + rb;
-      const double *const fz = tw + (int64_t)T_FZ * B;
-      const int b0 = nd_int(s.prev[2 * rb + 0]);
+      const double *const fz = tw + (int64_t)TK_FZ * B;
+      const int b0 = nlp_int(s.prev[2 * rb + 0]);
       {
         const double r = round(s.prev[2 * rb + 1] / dt);  // :933
-        ntd = nd_int(r) + 1;
+        ntd = nlp_int(r) + 1;
         ntd = ntd > ND_TAIL ? ND_TAIL : ntd;
       }
       // ---- the roll-out's ZMP (:938-951): jxx <= 3 are the tick's own bits
@@ -374,23 +248,23 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
       if (ntd > 3) {
         const bool poly = b0 >= 2;
         double co[7] = {0, 0, 0, 0, 0, 0, 0}, rt0 = 0.0;
-        if (poly) {  // CoM_height_solve (:2376-2429) with the previous tick's _bjx1
-          const double tsb = nd_at(ts, 1, b0 - 1);
+        // CoM_height_solve (:2376-2429) with the previous tick's _bjx1
+        if (poly) {
+          const double tsb = nlp_at(ts, 1, b0 - 1);
           const double tp3[3] = {0.0001, tsb / 2 + 0.0001, tsb + 0.0001};
           double pw[3][7], m[7][7], r[7][3];
 #pragma unroll
-          for (int q = 0; q < 3; ++q) nd_powers(tp3[q], pw[q]);
-          nd_fill(pw, m, r);
-          nd_lu<7, 3>(m, r);
-          nd_lu_solve<7, 3>(m, r);
-          const double z0 = nd_at(fz, B, b0 - 2), z1 = nd_at(fz, B, b0 - 1);
+          for (int q = 0; q < 3; ++q) nlp_powers(tp3[q], pw[q]);
+          nlp_aaa_fill(pw, m, r);
+          nlp_lu<7, 3>(m, r);
+          nlp_lu_solve<7, 3>(m, r);
+          const double z0 = nlp_at(fz, B, b0 - 2), z1 = nlp_at(fz, B, b0 - 1);
           const double p2 = z0 + hcom, p3 = (z0 + z1) / 2 + hcom, p4 = z1 + hcom;
 #pragma unroll
           for (int q = 0; q < 7; ++q) co[q] = ((0.0 + r[q][0] * p2) + r[q][1] * p3) + r[q][2] * p4;
-          rt0 = round(nd_at(tx, 1, b0 - 1) / dt);
+          rt0 = round(nlp_at(tx, 1, b0 - 1) / dt);
         }
-        // _Zsc(i + 3 .. i + 8), as qloco_nlp_tick.hip looks it up
-        int jz[ND_TAIL - 3];
+        int jz[ND_TAIL - 3];  // _Zsc(i + 3 .. i + 8)
         {
           bool g[ND_TAIL - 3];
 #pragma unroll
@@ -398,8 +272,8 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
             jz[q] = 0;
             g[q] = true;
           }
-          for (int k = 0; k < ND_NS; ++k) {
-            const double t = tw[(int64_t)(T_TX0 + k) * B];
+          for (int k = 0; k < NLP_NS; ++k) {
+            const double t = tw[(int64_t)(TK_TX0 + k) * B];
 #pragma unroll
             for (int q = 0; q < ND_TAIL - 3; ++q) {
               g[q] = g[q] && ((i + 4 + q) * dt >= t);
@@ -407,11 +281,11 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
             }
           }
         }
-        const int nsum = (ND_NS - 1) * nd_int(round(a.prm.tstep / dt));
+        const int nsum = (NLP_NS - 1) * nlp_int(round(a.prm.tstep / dt));
         const double Wn = sqrt(a.prm.g / (a.prm.z_c - 0.0));
-        const double xi = nd_at(fm + (int64_t)F_CXI * B, B, pi), vxi = nd_at(fm + (int64_t)F_CVXI * B, B, pi);
-        const double yi = nd_at(fm + (int64_t)F_CYI * B, B, pi), vyi = nd_at(fm + (int64_t)F_CVYI * B, B, pi);
-        const double px = nd_at(fm + (int64_t)F_FX * B, B, pi), py = nd_at(fm + (int64_t)F_FY * B, B, pi);
+        const double xi = nlp_at(fm + (int64_t)ST_CXI * B, B, pi), vxi = nlp_at(fm + (int64_t)ST_CVXI * B, B, pi);
+        const double yi = nlp_at(fm + (int64_t)ST_CYI * B, B, pi), vyi = nlp_at(fm + (int64_t)ST_CVYI * B, B, pi);
+        const double px = nlp_at(fm + (int64_t)ST_FX * B, B, pi), py = nlp_at(fm + (int64_t)ST_FY * B, B, pi);
 #pragma unroll
         for (int q = 3; q < ND_TAIL; ++q) {  // jxx = q + 1
           if (q < ntd) {
@@ -421,8 +295,8 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
             const double comax = (Wn * Wn) * xi * c + vxi * Wn * sn;
             const double comay = (Wn * Wn) * yi * c + vyi * Wn * sn;
             double cz = hcom, cvz = 0.0, caz = 0.0;  // Initialize's, where :2459-2467 write three entries only
-            if (poly) nd_poly(((double)(i + q + 1) - rt0) * dt, co, cz, cvz, caz);
-            const double zsc = (i + q >= nsum - 1) ? 0.0 : nd_at(fz, B, jz[q - 3] - 1);
+            if (poly) nlp_poly(((double)(i + q + 1) - rt0) * dt, co, cz, cvz, caz);
+            const double zsc = (i + q >= nsum - 1) ? 0.0 : nlp_at(fz, B, jz[q - 3] - 1);
             const double qq = (cz - zsc) / (caz + 9.8);
             nd_ring_wr(w, B, i + q, comx - qq * comax, comy - qq * comay);
           }
@@ -442,17 +316,17 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
       double cl[3], cr[3];
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        cl[k] = w[(int64_t)(N_COL + k) * B];
-        cr[k] = w[(int64_t)(N_COR + k) * B];
+        cl[k] = w[(int64_t)(ND_COL + k) * B];
+        cr[k] = w[(int64_t)(ND_COR + k) * B];
       }
       bool interp = false, swing_l = false;  // swing_l: the interpolated matrix is _Co_L
       double ix = 0.0, iy = 0.0, ex = 0.0, ey = 0.0;
       if (bjx1 >= 2) {
-        const double txb = nd_at(tx, 1, bjx1 - 1), tdb = nd_at(fm + (int64_t)F_TD * B, B, bjx1 - 1);
+        const double txb = nlp_at(tx, 1, bjx1 - 1), tdb = nlp_at(fm + (int64_t)ST_TD * B, B, bjx1 - 1);
         const double rt = round(txb / dt);
         swing_l = (bjx1 % 2) == 0;
         if (((double)(i + 1) - rt) * dt < tdb) {
-          const int n0 = nd_int(rt), n1 = nd_int(round((txb + tdb) / dt));
+          const int n0 = nlp_int(rt), n1 = nlp_int(round((txb + tdb) / dt));
           kend = n1 - 1;
           nd_ring_rd(w, B, n0 - 2, ix, iy);
           nd_ring_rd(w, B, kend, ex, ey);
@@ -468,10 +342,10 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) cl[k] = cr[k] = 0.5;
       } else {  // _footxyz_real, whose (1, 0) is -_stepwidth(0) (:1046)
-        ix = nd_at(fm + (int64_t)F_FX * B, B, bjx1 - 1);
-        iy = bjx1 == 1 ? -tw[(int64_t)T_SW0 * B] : nd_at(fm + (int64_t)F_FY * B, B, bjx1 - 1);
-        ex = nd_at(fm + (int64_t)F_FX * B, B, bjx1);
-        ey = nd_at(fm + (int64_t)F_FY * B, B, bjx1);
+        ix = nlp_at(fm + (int64_t)ST_FX * B, B, bjx1 - 1);
+        iy = bjx1 == 1 ? -tw[(int64_t)TK_SW0 * B] : nlp_at(fm + (int64_t)ST_FY * B, B, bjx1 - 1);
+        ex = nlp_at(fm + (int64_t)ST_FX * B, B, bjx1);
+        ey = nlp_at(fm + (int64_t)ST_FY * B, B, bjx1);
         interp = true;
       }
       if (interp) {
@@ -490,8 +364,8 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
       }
 #pragma unroll
       for (int k = 0; k < 3; ++k) {
-        w[(int64_t)(N_COL + k) * B] = cl[k];
-        w[(int64_t)(N_COR + k) * B] = cr[k];
+        w[(int64_t)(ND_COL + k) * B] = cl[k];
+        w[(int64_t)(ND_COR + k) * B] = cr[k];
       }
       // ---- Force_torque_calculate (:3872-3895): _thetaaxyx, _Lfootxyzx, _Rfootxyzx are zero
       double FL[3], FR[3], ML[3], MR[3];
@@ -548,7 +422,7 @@ __device__ __forceinline__ void nlp_node_robot(const NodeArgs &a, int64_t rb) {
     int32_t *const o = a.sched + QLOCO_NLP_NODE_SCHED_LEN * rb;
     o[0] = branch;
     o[2] = ti;
-    o[3] = nd_int(ROW(27));
+    o[3] = nlp_int(ROW(27));
     o[4] = status;
     o[6] = ntd;
     o[7] = kend;
@@ -564,7 +438,7 @@ __global__ __launch_bounds__(64) void nlp_node_post_kernel(const NodeArgs a) {
   const int64_t base = (int64_t)blockIdx.x * 64;
   const int64_t rb = base + threadIdx.x;
   if (rb < B) nlp_node_robot(a, rb);
-  const double *const rows = a.ws + (int64_t)N_ROW * B;
+  const double *const rows = a.ws + (int64_t)ND_ROW * B;
   if constexpr (FORM == 0) {
     if (rb >= B) return;
     for (int k = 0; k < ND_ROWLEN; ++k) a.gait[ND_ROWLEN * rb + k] = rows[(int64_t)k * B + rb];
@@ -590,24 +464,11 @@ __global__ __launch_bounds__(256) void nlp_node_init_kernel(int64_t B, double *w
   if (rb >= B) return;
   double *const w = ws + rb;
   for (int f = 0; f < ND_REC; ++f) w[(int64_t)f * B] = 0.0;
-  for (int s = 0; s < ND_RING; ++s) w[(int64_t)(N_RINGF + 3 * s) * B] = -1.0;
-  w[(int64_t)(N_ROW + 2) * B] = z_c;   // PelvisPos(2)
-  w[(int64_t)(N_ROW + 7) * B] = hw;    // LeftFootPosx(1)
-  w[(int64_t)(N_ROW + 10) * B] = -hw;  // RightFootPosx(1)
-  w[(int64_t)(N_ROW + 99) * B] = 2.0;  // right_support
-}
-
-template <bool SET>
-__global__ __launch_bounds__(256) void nlp_node_copy_kernel(int64_t B, double *ws, double *state) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= B * ND_REC) return;
-  const int64_t rb = t / ND_REC;
-  const int d = (int)(t % ND_REC);
-  double *w = ws + (int64_t)d * B + rb;
-  if (SET)
-    *w = state[t];
-  else
-    state[t] = *w;
+  for (int s = 0; s < ND_RING; ++s) w[(int64_t)(ND_RINGF + 3 * s) * B] = -1.0;
+  w[(int64_t)(ND_ROW + 2) * B] = z_c;   // PelvisPos(2)
+  w[(int64_t)(ND_ROW + 7) * B] = hw;    // LeftFootPosx(1)
+  w[(int64_t)(ND_ROW + 10) * B] = -hw;  // RightFootPosx(1)
+  w[(int64_t)(ND_ROW + 99) * B] = 2.0;  // right_support
 }
 
 }  // namespace qloco
@@ -641,8 +502,10 @@ extern "C" int qloco_nlp_node_set_form(int form) {
 
 static bool node_params_ok(const qloco_nlp_params *p, const qloco_nlp_tick_params *tp,
                            const qloco_nlp_node_params *np) {
-  if (!p || !tp || !np || !(p->dt > 0) || !(p->tstep > 0) || !(p->g > 0) || !(p->z_c > 0) || !(p->t_max > 0))
-    return false;
+  // The tick's checks first.  Its ring bound, round(t_max / dt) + 4 <= 48, rejects nothing the ND_TAIL bound
+  // below accepts (that one needs t_max / dt < 42.5).  Its hcom > 0 was not restated here before: both entry
+  // points returned QLOCO_ERR_ARG for it all the same, from the inner qloco_nlp_tick_init / qloco_nlp_tick.
+  if (!nlp_tick_params_ok(p, tp) || !np || !(p->t_max > 0)) return false;
   if (!(np->dtx == p->dt) || !(np->height_offset_time >= 0) || !(np->height_offset_time < 1.0e6) ||
       !(np->height_squat_time > 0) || !std::isfinite(np->height_offset) || !(np->totalmass > 0) ||
       !std::isfinite(np->rad))
@@ -652,7 +515,7 @@ static bool node_params_ok(const qloco_nlp_params *p, const qloco_nlp_tick_param
 }
 
 extern "C" int64_t qloco_nlp_node_workspace_bytes(int64_t batch) {
-  if (batch <= 0 || batch > kNodeMaxBatch) return -1;
+  if (batch <= 0 || batch > kNlpMaxBatch) return -1;
   return batch * (int64_t)(ND_REC + ND_SCR) * (int64_t)sizeof(double);
 }
 
@@ -660,7 +523,7 @@ extern "C" int qloco_nlp_node_init(const qloco_nlp_params *prm, const qloco_nlp_
                                    const qloco_nlp_node_params *node_prm, int64_t batch, void *nlp_workspace,
                                    void *tick_workspace, void *node_workspace, const double *steplength,
                                    const double *stepwidth, const double *stepheight, void *stream) {
-  if (!node_params_ok(prm, tick_prm, node_prm) || batch <= 0 || batch > kNodeMaxBatch || !node_workspace)
+  if (!node_params_ok(prm, tick_prm, node_prm) || batch <= 0 || batch > kNlpMaxBatch || !node_workspace)
     return QLOCO_ERR_ARG;
   const int r = qloco_nlp_tick_init(prm, tick_prm, batch, nlp_workspace, tick_workspace, steplength, stepwidth,
                                     stepheight, stream);
@@ -682,9 +545,9 @@ static void node_squat_coefficients(const qloco_nlp_params *prm, const qloco_nlp
     pw[q][0] = 1.0;
     for (int n = 1; n <= 6; ++n) pw[q][n] = std::pow(tp3[q], n);
   }
-  nd_fill(pw, m, r);
-  nd_lu<7, 3>(m, r);
-  nd_lu_solve<7, 3>(m, r);
+  nlp_aaa_fill(pw, m, r);
+  nlp_lu<7, 3>(m, r);
+  nlp_lu_solve<7, 3>(m, r);
   const double p2 = prm->z_c, p3 = prm->z_c - np->height_offset / 2, p4 = prm->z_c - np->height_offset;
   for (int q = 0; q < 7; ++q) co[q] = ((0.0 + r[q][0] * p2) + r[q][1] * p3) + r[q][2] * p4;
 }
@@ -693,7 +556,7 @@ extern "C" int qloco_nlp_node_tick(const qloco_nlp_params *prm, const qloco_nlp_
                                    const qloco_nlp_node_params *node_prm, int64_t batch, void *nlp_workspace,
                                    void *tick_workspace, void *node_workspace, const double *nrt_msg,
                                    double *gait_msg, int32_t *sched, int32_t *status, void *stream) {
-  if (!node_params_ok(prm, tick_prm, node_prm) || batch <= 0 || batch > kNodeMaxBatch || !nlp_workspace ||
+  if (!node_params_ok(prm, tick_prm, node_prm) || batch <= 0 || batch > kNlpMaxBatch || !nlp_workspace ||
       !tick_workspace || !node_workspace || !nrt_msg || !gait_msg)
     return QLOCO_ERR_ARG;
   NodeArgs a;
@@ -711,7 +574,7 @@ extern "C" int qloco_nlp_node_tick(const qloco_nlp_params *prm, const qloco_nlp_
   {
     // Get_maximal_number(_dtx) + 1 (:3026-3031, NLPRTControlClass.cpp:96)
     const int nT = (int)std::round(prm->tstep / prm->dt);
-    const int nsum = (ND_NS - 1) * nT, omit = 2 * (int)std::round(prm->tstep / prm->dt);
+    const int nsum = (NLP_NS - 1) * nT, omit = 2 * (int)std::round(prm->tstep / prm->dt);
     a.wmax = (int)((nsum - omit - 1) * std::floor(prm->dt / node_prm->dtx)) + 1;
     a.wsub = (int)node_prm->height_offset_time / node_prm->dtx;
     const double Wn = std::sqrt(prm->g / (prm->z_c - 0.0));
@@ -740,19 +603,9 @@ extern "C" int qloco_nlp_node_tick(const qloco_nlp_params *prm, const qloco_nlp_
 }
 
 extern "C" int qloco_nlp_node_get_state(int64_t batch, const void *node_workspace, double *state, void *stream) {
-  if (batch <= 0 || batch > kNodeMaxBatch || !node_workspace || !state) return QLOCO_ERR_ARG;
-  const int64_t n = batch * ND_REC;
-  hipLaunchKernelGGL(nlp_node_copy_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, batch, (double *)node_workspace, state);
-  QLOCO_HIP_CHECK(hipGetLastError(), "nlp_node_get_kernel launch");
-  return QLOCO_OK;
+  return nlp_record_copy<NlpNodeRecord, false>(batch, node_workspace, state, stream, "nlp_node_get_kernel launch");
 }
 
 extern "C" int qloco_nlp_node_set_state(int64_t batch, void *node_workspace, const double *state, void *stream) {
-  if (batch <= 0 || batch > kNodeMaxBatch || !node_workspace || !state) return QLOCO_ERR_ARG;
-  const int64_t n = batch * ND_REC;
-  hipLaunchKernelGGL(nlp_node_copy_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, batch, (double *)node_workspace, (double *)state);
-  QLOCO_HIP_CHECK(hipGetLastError(), "nlp_node_set_kernel launch");
-  return QLOCO_OK;
+  return nlp_record_copy<NlpNodeRecord, true>(batch, node_workspace, state, stream, "nlp_node_set_kernel launch");
 }

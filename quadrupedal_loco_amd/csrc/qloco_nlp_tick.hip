@@ -26,29 +26,21 @@
 // (qloco_nlp_tick_set_group_width).  Only the three columns of the inverse
 // that meet a non-zero of comz_plan are formed.
 //
-// Second workspace (doubles), field-major (field f of robot b at f B + b):
-//   0 previous _bjx1 | 1 _ry_left_right | 2 _t_end_footstep | 3 _stepwidth(0) |
-//   4 the last tick index | 5.. _footz_ref[27] | 32.. _lift_height_ref[27] |
-//   59.. the initial _tx[27] | 86.. a ring of QLOCO_NLP_TICK_RING entries of
-//   (Rfoot xyz, Lfoot xyz), array index k in entry k % RING;
-// then scratch the step-timing kernel writes when the caller passes no
-// buffer: com[B*18], sched[B*4] (int32), status[B] (int32).
+// Second workspace (doubles), field-major, the TK_ offsets of
+// qloco_nlp_core.hpp: previous _bjx1 | _ry_left_right | _t_end_footstep |
+// _stepwidth(0) | the last tick index | _footz_ref[27] | _lift_height_ref[27] |
+// the initial _tx[27] | a ring of (Rfoot xyz, Lfoot xyz), array index k in
+// entry k % RING; then the step-timing kernel's scratch.  The powers, the LU
+// and the bounded reads are that header's too.  The fill of AAA, the
+// polynomial and the _Zsc search are written out here in the order the kernel
+// was tuned in: calling the header's nlp_aaa_fill / nlp_poly instead gives the
+// same bits in another schedule (profiles/nlp_core_ab.txt).
 #include <atomic>
 #include <cstdlib>
 
-#include "qloco_common.hpp"
+#include "qloco_nlp_core.hpp"
 
 namespace qloco {
-
-constexpr int TK_NS = QLOCO_NLP_STEPS;
-constexpr int TK_RING = QLOCO_NLP_TICK_RING;
-constexpr int TK_REC = QLOCO_NLP_TICK_STATE;
-constexpr int64_t kTickMaxBatch = (int64_t)1 << 24;
-enum { T_BJX1 = 0, T_RY = 1, T_TEND = 2, T_SW0 = 3, T_LAST = 4, T_FZ = 5, T_LIFT = 32, T_TX0 = 59, T_RINGF = 86 };
-static_assert(T_RINGF + TK_RING * 6 == TK_REC, "record length");
-constexpr int TK_WS = TK_REC + 18 + 2 + 1;  // + com | sched | status scratch
-// fields of the section-14 record past ts / tx (qloco_nlp.hip)
-enum { N_TD = 0, N_LXX = 27, N_LYY = 54, N_FX = 81, N_FY = 108 };
 
 struct TickArgs {
   qloco_nlp_params prm;
@@ -63,12 +55,6 @@ struct TickArgs {
   int32_t *rs, *status;
 };
 
-__device__ __forceinline__ int tk_int(double v) { return (v > -1.0e9 && v < 1.0e9) ? (int)v : -1; }
-
-__device__ __forceinline__ double tk_at(const double *p, int64_t stride, int k) {
-  return (k >= 0 && k < TK_NS) ? p[(int64_t)k * stride] : __builtin_nan("");
-}
-
 // both feet's xyz at array index k: not yet written -> the values of
 // Initialize (:496-499); no longer held -> NaN
 __device__ __forceinline__ void tk_ring_rd(const double *w, int64_t B, int k, int last, double sw0, double (&o)[6]) {
@@ -80,87 +66,7 @@ __device__ __forceinline__ void tk_ring_rd(const double *w, int64_t B, int k, in
   } else {
     const int s = k % TK_RING;
 #pragma unroll
-    for (int c = 0; c < 6; ++c) o[c] = w[(int64_t)(T_RINGF + s * 6 + c) * B];
-  }
-}
-
-// t^2 .. t^6 as pow() returns them: each power is carried as an unevaluated
-// sum of two doubles (exact products through fma), so its leading part is the
-// correctly rounded value
-__device__ __forceinline__ void tk_powers(double t, double (&p)[7]) {
-  p[0] = 1.0;
-  p[1] = t;
-  double h = t * t, l = __builtin_fma(t, t, -h);
-  p[2] = h;
-#pragma unroll
-  for (int n = 3; n <= 6; ++n) {
-    const double q = h * t;
-    const double e = __builtin_fma(h, t, -q) + l * t;
-    h = q + e;
-    l = e - (h - q);
-    p[n] = h;
-  }
-}
-
-// partial-pivot LU of a (in place) with the rows of r carried along: the pivot
-// search and the swaps are selects over compile-time indices
-template <int N, int M>
-__device__ __forceinline__ void tk_lu(double (&a)[N][N], double (&r)[N][M]) {
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    int p = k;
-    double best = fabs(a[k][k]);
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      const double v = fabs(a[q][k]);
-      const bool g = v > best;
-      p = g ? q : p;
-      best = g ? v : best;
-    }
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      const bool s = p == q;
-#pragma unroll
-      for (int c = 0; c < N; ++c) {
-        const double x = a[k][c], y = a[q][c];
-        a[k][c] = s ? y : x;
-        a[q][c] = s ? x : y;
-      }
-#pragma unroll
-      for (int c = 0; c < M; ++c) {
-        const double x = r[k][c], y = r[q][c];
-        r[k][c] = s ? y : x;
-        r[q][c] = s ? x : y;
-      }
-    }
-#pragma unroll
-    for (int q = k + 1; q < N; ++q) {
-      a[q][k] = a[q][k] / a[k][k];
-#pragma unroll
-      for (int c = k + 1; c < N; ++c) a[q][c] = a[q][c] - a[q][k] * a[k][c];
-    }
-  }
-}
-
-// forward and back substitution of every column of r
-template <int N, int M>
-__device__ __forceinline__ void tk_lu_solve(const double (&a)[N][N], double (&r)[N][M]) {
-#pragma unroll
-  for (int m = 0; m < M; ++m) {
-#pragma unroll
-    for (int q = 0; q < N; ++q) {
-      double acc = r[q][m];
-#pragma unroll
-      for (int c = 0; c < q; ++c) acc = acc - a[q][c] * r[c][m];
-      r[q][m] = acc;
-    }
-#pragma unroll
-    for (int q = N - 1; q >= 0; --q) {
-      double acc = r[q][m];
-#pragma unroll
-      for (int c = q + 1; c < N; ++c) acc = acc - a[q][c] * r[c][m];
-      r[q][m] = acc / a[q][q];
-    }
+    for (int c = 0; c < 6; ++c) o[c] = w[(int64_t)(TK_RINGF + s * 6 + c) * B];
   }
 }
 
@@ -175,7 +81,7 @@ __device__ __forceinline__ void tk_height_cols_lane(const double (&tp3)[3], doub
   for (int q = 0; q < 7; ++q) {
     const double t = tp3[which[q]];
     double pw[7];
-    tk_powers(t, pw);
+    nlp_powers(t, pw);
     const double t2 = pw[2], t3 = pw[3], t4 = pw[4], t5 = pw[5], t6 = pw[6];
     if (kind[q] == 0) {
       m[q][0] = t6; m[q][1] = t5; m[q][2] = t4; m[q][3] = t3; m[q][4] = t2; m[q][5] = t; m[q][6] = 1.0;
@@ -187,21 +93,21 @@ __device__ __forceinline__ void tk_height_cols_lane(const double (&tp3)[3], doub
 #pragma unroll
     for (int c = 0; c < 3; ++c) r[q][c] = (q == c + 2) ? 1.0 : 0.0;  // columns 2, 3, 4 of the identity
   }
-  tk_lu<7, 3>(m, r);
-  tk_lu_solve<7, 3>(m, r);
+  nlp_lu<7, 3>(m, r);
+  nlp_lu_solve<7, 3>(m, r);
 }
 
 // the same three columns, one robot per 8-lane group: lane li < 7 holds row li
 // of the matrix and of the right-hand sides (lane 7 idles); the pivot search
 // reads column k of every row through cross-lane moves, the swap exchanges
-// two lanes' rows, and every row sees the operations of tk_lu / tk_lu_solve in
-// the same order, so the result is the lane form's, bit for bit.  Every lane
-// returns the full r.
+// two lanes' rows, and every row sees the operations of nlp_lu / nlp_lu_solve
+// in the same order, so the result is the lane form's, bit for bit.  Every
+// lane returns the full r.
 __device__ __forceinline__ void tk_height_cols_group(const double (&tp3)[3], int li, double (&r)[7][3]) {
   const int kind = (li == 0 || li == 5) ? 1 : ((li == 1 || li == 6) ? 2 : 0);
   const double t = li < 3 ? tp3[0] : (li == 3 ? tp3[1] : tp3[2]);
   double pw[7];
-  tk_powers(t, pw);
+  nlp_powers(t, pw);
   const double t2 = pw[2], t3 = pw[3], t4 = pw[4], t5 = pw[5], t6 = pw[6];
   double row[7], rr[3];
   row[0] = kind == 0 ? t6 : (kind == 1 ? 6 * t5 : 30 * t4);
@@ -271,9 +177,9 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
   if (rb >= a.batch) return;
   const int64_t B = a.batch;
   const double nan = __builtin_nan("");
-  const double *const ts = a.nws + rb * TK_NS;
-  const double *const tx = a.nws + B * TK_NS + rb * TK_NS;
-  const double *const fm = a.nws + 2 * B * TK_NS + rb;  // section-14 field f at fm[f * B]
+  const double *const ts = a.nws + rb * NLP_NS;
+  const double *const tx = a.nws + B * NLP_NS + rb * NLP_NS;
+  const double *const fm = a.nws + 2 * B * NLP_NS + rb;  // section-14 field f at fm[f * B]
   double *const w = a.tws + rb;                          // field f at w[f * B]
   double *const ct = a.com_traj + 38 * rb;
   double *const rl = a.rlfoot + 18 * rb;
@@ -293,27 +199,27 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
   const double *const com = a.com + 18 * rb;
 
   // ---- CoM_height_solve (:2361-2473) with the previous tick's _bjx1
-  const int b0 = tk_int(w[(int64_t)T_BJX1 * B]);
+  const int b0 = nlp_int(w[(int64_t)TK_BJX1 * B]);
   double cz[3] = {hcom, hcom, hcom}, cvz[3] = {0.0, 0.0, 0.0}, caz[3] = {0.0, 0.0, 0.0};
   if (b0 >= 2) {
-    const double tsb = tk_at(ts, 1, b0 - 1);
+    const double tsb = nlp_at(ts, 1, b0 - 1);
     const double tp3[3] = {0.0001, tsb / 2 + 0.0001, tsb + 0.0001};
     double r[7][3];  // columns 2, 3, 4 of AAA.inverse()
     if constexpr (GW == 1)
       tk_height_cols_lane(tp3, r);
     else
       tk_height_cols_group(tp3, li, r);
-    const double z0 = tk_at(w + (int64_t)T_FZ * B, B, b0 - 2), z1 = tk_at(w + (int64_t)T_FZ * B, B, b0 - 1);
+    const double z0 = nlp_at(w + (int64_t)TK_FZ * B, B, b0 - 2), z1 = nlp_at(w + (int64_t)TK_FZ * B, B, b0 - 1);
     const double p2 = z0 + hcom, p3 = (z0 + z1) / 2 + hcom, p4 = z1 + hcom;
     double co[7];
 #pragma unroll
     for (int q = 0; q < 7; ++q) co[q] = ((0.0 + r[q][0] * p2) + r[q][1] * p3) + r[q][2] * p4;
-    const double rt0 = round(tk_at(tx, 1, b0 - 1) / dt);
+    const double rt0 = round(nlp_at(tx, 1, b0 - 1) / dt);
 #pragma unroll
     for (int s = 0; s < 3; ++s) {
       const double t = ((double)(i + s + 1) - rt0) * dt;
       double pw[7];
-      tk_powers(t, pw);
+      nlp_powers(t, pw);
       const double t2 = pw[2], t3 = pw[3], t4 = pw[4], t5 = pw[5], t6 = pw[6];
       cz[s] = (((((t6 * co[0] + t5 * co[1]) + t4 * co[2]) + t3 * co[3]) + t2 * co[4]) + t * co[5]) + 1.0 * co[6];
       cvz[s] = ((((((6 * t5) * co[0] + (5 * t4) * co[1]) + (4 * t3) * co[2]) + (3 * t2) * co[3]) + (2 * t) * co[4]) +
@@ -321,18 +227,18 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
       caz[s] = ((((((30 * t4) * co[0] + (20 * t3) * co[1]) + (12 * t2) * co[2]) + (6 * t) * co[3]) + 2.0 * co[4]) +
                 0.0 * co[5]) + 0.0 * co[6];
     }
-  }
+    }
   if (!wr) return;  // the group's other lanes only carry rows of the 7 x 7 system
-  w[(int64_t)T_BJX1 * B] = (double)bjx1;  // :1038
+  w[(int64_t)TK_BJX1 * B] = (double)bjx1;  // :1038
 
   // ---- _Zsc(i), (i + 1), (i + 2): _footz_ref of the step (k + 1) dt falls in under the initial _tx
   double zs[3];
   {
-    const int nsum = (TK_NS - 1) * tk_int(round(a.prm.tstep / dt));
+    const int nsum = (NLP_NS - 1) * nlp_int(round(a.prm.tstep / dt));
     int j0 = 0, j1 = 0, j2 = 0;
     bool g0 = true, g1 = true, g2 = true;
-    for (int k = 0; k < TK_NS; ++k) {
-      const double t = w[(int64_t)(T_TX0 + k) * B];
+    for (int k = 0; k < NLP_NS; ++k) {
+      const double t = w[(int64_t)(TK_TX0 + k) * B];
       g0 = g0 && ((i + 1) * dt >= t);
       g1 = g1 && ((i + 2) * dt >= t);
       g2 = g2 && ((i + 3) * dt >= t);
@@ -340,10 +246,10 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
       j1 += g1 ? 1 : 0;
       j2 += g2 ? 1 : 0;
     }
-    const double *const fz = w + (int64_t)T_FZ * B;
-    zs[0] = (i + 0 >= nsum - 1) ? 0.0 : tk_at(fz, B, j0 - 1);
-    zs[1] = (i + 1 >= nsum - 1) ? 0.0 : tk_at(fz, B, j1 - 1);
-    zs[2] = (i + 2 >= nsum - 1) ? 0.0 : tk_at(fz, B, j2 - 1);
+    const double *const fz = w + (int64_t)TK_FZ * B;
+    zs[0] = (i + 0 >= nsum - 1) ? 0.0 : nlp_at(fz, B, j0 - 1);
+    zs[1] = (i + 1 >= nsum - 1) ? 0.0 : nlp_at(fz, B, j1 - 1);
+    zs[2] = (i + 2 >= nsum - 1) ? 0.0 : nlp_at(fz, B, j2 - 1);
   }
   // ---- :950-954 and the 38-vector :1048-1090
   bool fin = true;
@@ -378,13 +284,13 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
   ct[25] = com[17];
   ct[26] = caz[2];
   ct[27] = (double)bjxx;
-  const double *const fxp = fm + (int64_t)N_FX * B, *const fyp = fm + (int64_t)N_FY * B;
-  const double *const fzp = w + (int64_t)T_FZ * B;
+  const double *const fxp = fm + (int64_t)ST_FX * B, *const fyp = fm + (int64_t)ST_FY * B;
+  const double *const fzp = w + (int64_t)TK_FZ * B;
   {
-    const bool in = bjxx >= 0 && bjxx + 1 < TK_NS;
-    const double v28 = in ? tk_at(fxp, B, bjxx) : nan, v29 = in ? tk_at(fxp, B, bjxx + 1) : nan;
-    const double v30 = in ? tk_at(fyp, B, bjxx) : nan, v31 = in ? tk_at(fyp, B, bjxx + 1) : nan;
-    const double v32 = in ? tk_at(fzp, B, bjxx) : nan, v33 = in ? tk_at(fzp, B, bjxx + 1) : nan;
+    const bool in = bjxx >= 0 && bjxx + 1 < NLP_NS;
+    const double v28 = in ? nlp_at(fxp, B, bjxx) : nan, v29 = in ? nlp_at(fxp, B, bjxx + 1) : nan;
+    const double v30 = in ? nlp_at(fyp, B, bjxx) : nan, v31 = in ? nlp_at(fyp, B, bjxx + 1) : nan;
+    const double v32 = in ? nlp_at(fzp, B, bjxx) : nan, v33 = in ? nlp_at(fzp, B, bjxx + 1) : nan;
     ct[28] = v28;
     ct[29] = v29;
     ct[30] = v30;
@@ -394,8 +300,8 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
     if (in) fin = fin && isfinite(v28) && isfinite(v29) && isfinite(v30) && isfinite(v31) && isfinite(v32) && isfinite(v33);
   }
   {
-    const double v35 = tk_at(ts, 1, period - 1), v36 = tk_at(fm + (int64_t)N_LXX * B, B, period - 1);
-    const double v37 = tk_at(fm + (int64_t)N_LYY * B, B, period - 1);
+    const double v35 = nlp_at(ts, 1, period - 1), v36 = nlp_at(fm + (int64_t)ST_LXX * B, B, period - 1);
+    const double v37 = nlp_at(fm + (int64_t)ST_LYY * B, B, period - 1);
     ct[34] = (double)(period - 1);
     ct[35] = v35;
     ct[36] = v36;
@@ -404,20 +310,20 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
   }
 
   // ---- Foot_trajectory_solve_mod2 (:2039-2358)
-  const int t_end = tk_int(w[(int64_t)T_TEND * B]);
-  const double sw0 = w[(int64_t)T_SW0 * B];
-  const int last = tk_int(w[(int64_t)T_LAST * B]);
+  const int t_end = nlp_int(w[(int64_t)TK_TEND * B]);
+  const double sw0 = w[(int64_t)TK_SW0 * B];
+  const int last = nlp_int(w[(int64_t)TK_LAST * B]);
   const bool stop = a.stop ? a.stop[rb] != 0 : false;
   if (stop || i > t_end)  // :2043-2050
-    for (int k = (bjx1 + 1 > 0 ? bjx1 + 1 : 0); k < TK_NS; ++k) w[(int64_t)(T_LIFT + k) * B] = 0.0;
+    for (int k = (bjx1 + 1 > 0 ? bjx1 + 1 : 0); k < NLP_NS; ++k) w[(int64_t)(TK_LIFT + k) * B] = 0.0;
   double cur[6], nxt[6], vel[6] = {0, 0, 0, 0, 0, 0}, acc[6] = {0, 0, 0, 0, 0, 0};
   int rs = 2;
   if (bjx1 >= 2 && i <= t_end) {  // :2076
     const int b = bjx1;
-    const double txb = tk_at(tx, 1, b - 1), tsb = tk_at(ts, 1, b - 1), tdb = tk_at(fm + (int64_t)N_TD * B, B, b - 1);
+    const double txb = nlp_at(tx, 1, b - 1), tsb = nlp_at(ts, 1, b - 1), tdb = nlp_at(fm + (int64_t)ST_TD * B, B, b - 1);
     const double rt = round(txb / dt);
     double H[6];
-    tk_ring_rd(w, B, (rt == rt) ? tk_int(rt) - 2 : -1, last, sw0, H);
+    tk_ring_rd(w, B, (rt == rt) ? nlp_int(rt) - 2 : -1, last, sw0, H);
     const bool swr = (b % 2) == 0;  // the right foot swings (left support)
     rs = swr ? 0 : 1;
     double sg[3], sn[3], sv[3] = {0, 0, 0}, sa[3] = {0, 0, 0};  // swing foot: at j, at j + 1, velocity, acceleration
@@ -428,7 +334,7 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
       for (int c = 0; c < 3; ++c) sg[c] = sn[c] = swr ? H[c] : H[3 + c];
     } else {
       const double t_des = ((double)(i + 1) - rt + 1) * dt;
-      const double f2x = tk_at(fxp, B, bjxx), f2y = bjxx == 0 ? -sw0 : tk_at(fyp, B, bjxx), f2z = tk_at(fzp, B, bjxx);
+      const double f2x = nlp_at(fxp, B, bjxx), f2y = bjxx == 0 ? -sw0 : nlp_at(fyp, B, bjxx), f2z = nlp_at(fzp, B, bjxx);
       if (fabs(t_des - tsb) <= 0.0005) {  // :2113, :2226: landing
         sg[0] = sn[0] = f2x;
         sg[1] = sn[1] = f2y;
@@ -450,14 +356,14 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
         m[3][3] = 0.0;
         double P[6];
         tk_ring_rd(w, B, i - 1, last, sw0, P);
-        const double f0x = tk_at(fxp, B, bjxx - 2), f0y = bjxx == 2 ? -sw0 : tk_at(fyp, B, bjxx - 2);
-        const double f0z = tk_at(fzp, B, bjxx - 2);
-        double ry = w[(int64_t)T_RY * B];
+        const double f0x = nlp_at(fxp, B, bjxx - 2), f0y = bjxx == 2 ? -sw0 : nlp_at(fyp, B, bjxx - 2);
+        const double f0z = nlp_at(fzp, B, bjxx - 2);
+        double ry = w[(int64_t)TK_RY * B];
         if (((double)(i + 1) - rt) * dt < tdb + dt) {  // :2150, :2268
           ry = (f2y + f0y) / 2;
-          w[(int64_t)T_RY * B] = ry;
+          w[(int64_t)TK_RY * B] = ry;
         }
-        const double zmid = (f0z < f2z ? f2z : f0z) + tk_at(w + (int64_t)T_LIFT * B, B, b - 1);
+        const double zmid = (f0z < f2z ? f2z : f0z) + nlp_at(w + (int64_t)TK_LIFT * B, B, b - 1);
         const double plan[3][3] = {{swr ? P[0] : P[3], (f0x + f2x) / 2, f2x},
                                    {swr ? P[1] : P[4], ry, f2y},
                                    {swr ? P[2] : P[5], zmid, f2z}};
@@ -470,8 +376,8 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
           rh[2][ax] = plan[ax][2];
           rh[3][ax] = 0.0;
         }
-        tk_lu<4, 3>(m, rh);
-        tk_lu_solve<4, 3>(m, rh);
+        nlp_lu<4, 3>(m, rh);
+        nlp_lu_solve<4, 3>(m, rh);
         const double t = t_des, t2 = t * t, t3 = t2 * t;
 #pragma unroll
         for (int ax = 0; ax < 3; ++ax) {
@@ -512,10 +418,10 @@ __global__ __launch_bounds__(64) void nlp_tick_kernel(const TickArgs a) {
     const int s0 = i % TK_RING, s1 = (i + 1) % TK_RING;  // i >= 1 here
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-      w[(int64_t)(T_RINGF + s0 * 6 + c) * B] = cur[c];
-      w[(int64_t)(T_RINGF + s1 * 6 + c) * B] = nxt[c];
+      w[(int64_t)(TK_RINGF + s0 * 6 + c) * B] = cur[c];
+      w[(int64_t)(TK_RINGF + s1 * 6 + c) * B] = nxt[c];
     }
-    w[(int64_t)T_LAST * B] = (double)i;
+    w[(int64_t)TK_LAST * B] = (double)i;
   }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
@@ -538,44 +444,30 @@ __global__ __launch_bounds__(256) void nlp_tick_init_kernel(int64_t B, double *w
   double *const w = ws + rb;
   const double sw0 = stepwidth[rb] / 2, sh = stepheight ? stepheight[rb] : 0.0;
   double z = 0.0, t = 0.0;
-  for (int j = 0; j < TK_NS; ++j) {
-    w[(int64_t)(T_FZ + j) * B] = z;
+  for (int j = 0; j < NLP_NS; ++j) {
+    w[(int64_t)(TK_FZ + j) * B] = z;
     z = z + sh;
     double lh = lift_height;
-    if (j >= TK_NS - 2) lh = 0.0;
-    if (j == TK_NS - 3) lh = lift_height / 2;
-    w[(int64_t)(T_LIFT + j) * B] = lh;
-    w[(int64_t)(T_TX0 + j) * B] = t;
-    if (j == TK_NS - 1) w[(int64_t)T_TEND * B] = round((t - 2 * tstep) / dt);
+    if (j >= NLP_NS - 2) lh = 0.0;
+    if (j == NLP_NS - 3) lh = lift_height / 2;
+    w[(int64_t)(TK_LIFT + j) * B] = lh;
+    w[(int64_t)(TK_TX0 + j) * B] = t;
+    if (j == NLP_NS - 1) w[(int64_t)TK_TEND * B] = round((t - 2 * tstep) / dt);
     t = t + tstep;
     t = round(t / dt) * dt - 0.000001;
   }
-  w[(int64_t)T_BJX1 * B] = 0.0;
-  w[(int64_t)T_RY * B] = 0.0;
-  w[(int64_t)T_SW0 * B] = sw0;
-  w[(int64_t)T_LAST * B] = 0.0;
+  w[(int64_t)TK_BJX1 * B] = 0.0;
+  w[(int64_t)TK_RY * B] = 0.0;
+  w[(int64_t)TK_SW0 * B] = sw0;
+  w[(int64_t)TK_LAST * B] = 0.0;
   for (int s = 0; s < TK_RING; ++s) {
-    w[(int64_t)(T_RINGF + s * 6 + 0) * B] = 0.0;
-    w[(int64_t)(T_RINGF + s * 6 + 1) * B] = -sw0;
-    w[(int64_t)(T_RINGF + s * 6 + 2) * B] = 0.0;
-    w[(int64_t)(T_RINGF + s * 6 + 3) * B] = 0.0;
-    w[(int64_t)(T_RINGF + s * 6 + 4) * B] = sw0;
-    w[(int64_t)(T_RINGF + s * 6 + 5) * B] = 0.0;
+    w[(int64_t)(TK_RINGF + s * 6 + 0) * B] = 0.0;
+    w[(int64_t)(TK_RINGF + s * 6 + 1) * B] = -sw0;
+    w[(int64_t)(TK_RINGF + s * 6 + 2) * B] = 0.0;
+    w[(int64_t)(TK_RINGF + s * 6 + 3) * B] = 0.0;
+    w[(int64_t)(TK_RINGF + s * 6 + 4) * B] = sw0;
+    w[(int64_t)(TK_RINGF + s * 6 + 5) * B] = 0.0;
   }
-}
-
-// dense record <-> workspace, one thread per value
-template <bool SET>
-__global__ __launch_bounds__(256) void nlp_tick_copy_kernel(int64_t B, double *ws, double *state) {
-  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= B * TK_REC) return;
-  const int64_t rb = t / TK_REC;
-  const int d = (int)(t % TK_REC);
-  double *w = ws + (int64_t)d * B + rb;
-  if (SET)
-    *w = state[t];
-  else
-    state[t] = *w;
 }
 
 }  // namespace qloco
@@ -601,22 +493,15 @@ extern "C" int qloco_nlp_tick_set_group_width(int gw) {
   return g_tick_gw.exchange(gw);
 }
 
-static bool tick_params_ok(const qloco_nlp_params *p, const qloco_nlp_tick_params *tp) {
-  if (!p || !tp || !(p->dt > 0) || !(p->tstep > 0) || !(p->g > 0) || !(p->z_c > 0) || !(tp->hcom > 0)) return false;
-  // the ring holds round(t_max / dt) ticks of a step, the two-tick look-back and the forecast slot
-  const double n = round(p->t_max / p->dt);
-  return n >= 0 && n + 4 <= TK_RING;
-}
-
 extern "C" int64_t qloco_nlp_tick_workspace_bytes(int64_t batch) {
-  if (batch <= 0 || batch > kTickMaxBatch) return -1;
+  if (batch <= 0 || batch > kNlpMaxBatch) return -1;
   return batch * (int64_t)TK_WS * (int64_t)sizeof(double);
 }
 
 extern "C" int qloco_nlp_tick_init(const qloco_nlp_params *prm, const qloco_nlp_tick_params *tick_prm, int64_t batch,
                                    void *nlp_workspace, void *tick_workspace, const double *steplength,
                                    const double *stepwidth, const double *stepheight, void *stream) {
-  if (!tick_params_ok(prm, tick_prm) || batch <= 0 || batch > kTickMaxBatch || !nlp_workspace || !tick_workspace ||
+  if (!nlp_tick_params_ok(prm, tick_prm) || batch <= 0 || batch > kNlpMaxBatch || !nlp_workspace || !tick_workspace ||
       !steplength || !stepwidth)
     return QLOCO_ERR_ARG;
   const int r = qloco_nlp_init(prm, batch, nlp_workspace, steplength, stepwidth, stepheight, stream);
@@ -635,14 +520,14 @@ extern "C" int qloco_nlp_tick(const qloco_nlp_params *prm, const qloco_nlp_tick_
                               double *rlfoot_traj, int32_t *right_support, double *vari_ini, int32_t *sched,
                               double *step, double *com, int32_t *pass_status, int32_t *pass_iters, int32_t *status,
                               void *stream) {
-  if (!tick_params_ok(prm, tick_prm) || batch <= 0 || batch > kTickMaxBatch || !nlp_workspace || !tick_workspace ||
+  if (!nlp_tick_params_ok(prm, tick_prm) || batch <= 0 || batch > kNlpMaxBatch || !nlp_workspace || !tick_workspace ||
       !t_int || !estimated_state || !rfoot_feedback || !lfoot_feedback || !com_traj || !rlfoot_traj ||
       !right_support || !vari_ini)
     return QLOCO_ERR_ARG;
   double *const tws = (double *)tick_workspace;
-  double *const com_s = com ? com : tws + (int64_t)TK_REC * batch;
-  int32_t *const sched_s = sched ? sched : (int32_t *)(tws + (int64_t)(TK_REC + 18) * batch);
-  int32_t *const st_s = (int32_t *)(tws + (int64_t)(TK_REC + 20) * batch);
+  double *const com_s = com ? com : tws + (int64_t)TK_S_COM * batch;
+  int32_t *const sched_s = sched ? sched : (int32_t *)(tws + (int64_t)TK_S_SCHED * batch);
+  int32_t *const st_s = (int32_t *)(tws + (int64_t)TK_S_STATUS * batch);
   const int r = qloco_nlp_step_timing(prm, batch, nlp_workspace, t_int, estimated_state, rfoot_feedback,
                                       lfoot_feedback, vari_ini, sched_s, step, com_s, pass_status, pass_iters, st_s,
                                       stream);
@@ -671,19 +556,9 @@ extern "C" int qloco_nlp_tick(const qloco_nlp_params *prm, const qloco_nlp_tick_
 }
 
 extern "C" int qloco_nlp_tick_get_state(int64_t batch, const void *tick_workspace, double *state, void *stream) {
-  if (batch <= 0 || batch > kTickMaxBatch || !tick_workspace || !state) return QLOCO_ERR_ARG;
-  const int64_t n = batch * TK_REC;
-  hipLaunchKernelGGL(nlp_tick_copy_kernel<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, batch, (double *)tick_workspace, state);
-  QLOCO_HIP_CHECK(hipGetLastError(), "nlp_tick_get_kernel launch");
-  return QLOCO_OK;
+  return nlp_record_copy<NlpTickRecord, false>(batch, tick_workspace, state, stream, "nlp_tick_get_kernel launch");
 }
 
 extern "C" int qloco_nlp_tick_set_state(int64_t batch, void *tick_workspace, const double *state, void *stream) {
-  if (batch <= 0 || batch > kTickMaxBatch || !tick_workspace || !state) return QLOCO_ERR_ARG;
-  const int64_t n = batch * TK_REC;
-  hipLaunchKernelGGL(nlp_tick_copy_kernel<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                     (hipStream_t)stream, batch, (double *)tick_workspace, (double *)state);
-  QLOCO_HIP_CHECK(hipGetLastError(), "nlp_tick_set_kernel launch");
-  return QLOCO_OK;
+  return nlp_record_copy<NlpTickRecord, true>(batch, tick_workspace, state, stream, "nlp_tick_set_kernel launch");
 }

@@ -42,16 +42,30 @@ STATE_FIELDS = dict(  # slices of the dense record get_state / set_state use
     COMvy_is=(270, 297), vari=(297, 301), feed=(301, 307), endref=(307, 309))
 
 
-def default_params(**overrides):
-    """NLPClass.h:32-37, the "go1" branch of Initialize and the constants
-    NLPRTControlClass.cpp:33-56 passes."""
-    p = NlpParams()
-    lib().qloco_nlp_params_default(C.byref(p))
+def _defaults(struct, fill, overrides):
+    """The library's default parameter struct (qloco_<fill>) with overrides."""
+    p = struct()
+    getattr(lib(), "qloco_" + fill)(C.byref(p))
     for k, v in overrides.items():
         if k == "reserved" or not hasattr(p, k):
             raise ValueError("unknown parameter %s" % k)
         setattr(p, k, v)
     return p
+
+
+def _workspace(sizer, batch, device):
+    """A zeroed float64 workspace of qloco_<sizer>(batch) bytes."""
+    import torch
+    nbytes = getattr(lib(), "qloco_" + sizer)(int(batch))
+    if nbytes <= 0:
+        raise ValueError("qloco_%s(%d) = %d" % (sizer, batch, nbytes))
+    return torch.zeros(nbytes // 8, dtype=torch.float64, device=torch.device(device))
+
+
+def default_params(**overrides):
+    """NLPClass.h:32-37, the "go1" branch of Initialize and the constants
+    NLPRTControlClass.cpp:33-56 passes."""
+    return _defaults(NlpParams, "nlp_params_default", overrides)
 
 
 @dataclass
@@ -76,10 +90,7 @@ class StepTimingPlanner:
         self.batch = int(batch)
         self.device = torch.device(device)
         self.params = params if params is not None else default_params(**overrides)
-        nbytes = lib().qloco_nlp_workspace_bytes(self.batch)
-        if nbytes <= 0:
-            raise ValueError("qloco_nlp_workspace_bytes(%d) = %d" % (self.batch, nbytes))
-        self.workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=self.device)
+        self.workspace = _workspace("nlp_workspace_bytes", self.batch, self.device)
         B = self.batch
         self.ts = self.workspace[:B * NS].view(B, NS)            # _ts, a row per robot
         self.tx = self.workspace[B * NS:2 * B * NS].view(B, NS)  # _tx
@@ -95,6 +106,20 @@ class StepTimingPlanner:
     def _f64(self, *shape):
         import torch
         return torch.empty(shape, dtype=torch.float64, device=self.device)
+
+    def _i32(self, *shape):
+        import torch
+        return torch.empty(shape, dtype=torch.int32, device=self.device)
+
+    def _step_timing_result(self):
+        B = self.batch
+        return StepTimingResult(self._f64(B, 4), self._i32(B, 4), self._f64(B, 3), self._f64(B, 18), self._i32(B, 3),
+                                self._i32(B, 3), self._i32(B))
+
+    def _record(self, fn, workspace, state, stream):
+        """qloco_nlp*_get_state / _set_state: `state` is the dense (B, n) record."""
+        check(getattr(lib(), fn)(self.batch, ptr(workspace), ptr(state), self._stream(stream)), fn)
+        return state
 
     def _per_robot(self, v, name):
         import torch
@@ -112,16 +137,13 @@ class StepTimingPlanner:
     def tick(self, t_int, estimated_state, rfoot_feedback, lfoot_feedback, out=None, stream=None):
         """One planner tick: t_int (B,) int32, estimated_state (B, 6),
         rfoot_feedback / lfoot_feedback (B, 2), device tensors."""
-        import torch
         B = self.batch
         _dev(t_int, "i32", (B,), "t_int")
         _dev(estimated_state, "f64", (B, 6), "estimated_state")
         _dev(rfoot_feedback, "f64", (B, 2), "rfoot_feedback")
         _dev(lfoot_feedback, "f64", (B, 2), "lfoot_feedback")
         if out is None:
-            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)
-            out = StepTimingResult(self._f64(B, 4), i32(B, 4), self._f64(B, 3), self._f64(B, 18), i32(B, 3),
-                                   i32(B, 3), i32(B))
+            out = self._step_timing_result()
         check(lib().qloco_nlp_step_timing(
             C.byref(self.params), B, ptr(self.workspace), ptr(t_int), ptr(estimated_state),
             ptr(rfoot_feedback), ptr(lfoot_feedback), ptr(out.vari_ini), ptr(out.sched), ptr(out.step),
@@ -131,15 +153,10 @@ class StepTimingPlanner:
 
     def get_state(self, stream=None):
         """Dense (B, 309) record per robot (STATE_FIELDS)."""
-        s = self._f64(self.batch, STATE)
-        check(lib().qloco_nlp_get_state(self.batch, ptr(self.workspace), ptr(s), self._stream(stream)),
-              "qloco_nlp_get_state")
-        return s
+        return self._record("qloco_nlp_get_state", self.workspace, self._f64(self.batch, STATE), stream)
 
     def set_state(self, state, stream=None):
-        _dev(state, "f64", (self.batch, STATE), "state")
-        check(lib().qloco_nlp_set_state(self.batch, ptr(self.workspace), ptr(state), self._stream(stream)),
-              "qloco_nlp_set_state")
+        self._record("qloco_nlp_set_state", self.workspace, _dev(state, "f64", (self.batch, STATE), "state"), stream)
 
 
 TICK_STATE = 374      # QLOCO_NLP_TICK_STATE
@@ -151,13 +168,7 @@ TICK_STATE_FIELDS = dict(  # slices of the dense record of the second workspace
 
 def default_tick_params(**overrides):
     """_lift_height (NLPRTControlClass.cpp:48) and _hcom (NLPClass_sqp.cpp:212)."""
-    p = NlpTickParams()
-    lib().qloco_nlp_tick_params_default(C.byref(p))
-    for k, v in overrides.items():
-        if k == "reserved" or not hasattr(p, k):
-            raise ValueError("unknown parameter %s" % k)
-        setattr(p, k, v)
-    return p
+    return _defaults(NlpTickParams, "nlp_tick_params_default", overrides)
 
 
 @dataclass
@@ -177,27 +188,25 @@ class PlannerTick(StepTimingPlanner):
 
     def __init__(self, batch, device, params=None, tick_params=None, steplength=0.075, stepwidth=None,
                  stepheight=None, **overrides):
-        import torch
         self.tick_params = tick_params if tick_params is not None else default_tick_params()
-        nbytes = lib().qloco_nlp_tick_workspace_bytes(int(batch))
-        if nbytes <= 0:
-            raise ValueError("qloco_nlp_tick_workspace_bytes(%d) = %d" % (batch, nbytes))
-        self.tick_workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=torch.device(device))
+        self.tick_workspace = _workspace("nlp_tick_workspace_bytes", batch, device)
         self._stepheight = stepheight
         super().__init__(batch, device, params=params, steplength=steplength, stepwidth=stepwidth, **overrides)
 
     def init(self, steplength, stepwidth, stepheight=None, stream=None):
         """FootStepInputs + Initialize of both records: scalars or per-robot
         (B,) values; stepheight None is flat ground."""
-        sl = self._per_robot(steplength, "steplength")
-        sw = self._per_robot(stepwidth, "stepwidth")
-        if stepheight is None:
-            stepheight = self._stepheight
-        sh = None if stepheight is None else self._per_robot(stepheight, "stepheight")
+        sl, sw, sh = self._step_inputs(steplength, stepwidth, stepheight)
         check(lib().qloco_nlp_tick_init(C.byref(self.params), C.byref(self.tick_params), self.batch,
                                         ptr(self.workspace), ptr(self.tick_workspace), ptr(sl), ptr(sw),
                                         None if sh is None else ptr(sh), self._stream(stream)),
               "qloco_nlp_tick_init")
+
+    def _step_inputs(self, steplength, stepwidth, stepheight):
+        if stepheight is None:
+            stepheight = self._stepheight
+        return (self._per_robot(steplength, "steplength"), self._per_robot(stepwidth, "stepwidth"),
+                None if stepheight is None else self._per_robot(stepheight, "stepheight"))
 
     def step_timing_tick(self, t_int, estimated_state, rfoot_feedback, lfoot_feedback, out=None, stream=None):
         """The SQP alone (StepTimingPlanner.tick): the second record is not advanced."""
@@ -208,7 +217,6 @@ class PlannerTick(StepTimingPlanner):
         """One planner tick: the inputs of StepTimingPlanner.tick and an
         optional stop_walking (B,) int32.  out: a PlannerTickResult of an
         earlier call to write into."""
-        import torch
         B = self.batch
         _dev(t_int, "i32", (B,), "t_int")
         _dev(estimated_state, "f64", (B, 6), "estimated_state")
@@ -217,10 +225,8 @@ class PlannerTick(StepTimingPlanner):
         if stop_walking is not None:
             _dev(stop_walking, "i32", (B,), "stop_walking")
         if out is None:
-            i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=self.device)
-            st = StepTimingResult(self._f64(B, 4), i32(B, 4), self._f64(B, 3), self._f64(B, 18), i32(B, 3),
-                                  i32(B, 3), i32(B))
-            out = PlannerTickResult(self._f64(B, 38), self._f64(B, 18), i32(B), st.status, st)
+            st = self._step_timing_result()
+            out = PlannerTickResult(self._f64(B, 38), self._f64(B, 18), self._i32(B), st.status, st)
         st = out.step_timing
         check(lib().qloco_nlp_tick(
             C.byref(self.params), C.byref(self.tick_params), B, ptr(self.workspace), ptr(self.tick_workspace),
@@ -232,15 +238,11 @@ class PlannerTick(StepTimingPlanner):
 
     def get_tick_state(self, stream=None):
         """Dense (B, 374) second record per robot (TICK_STATE_FIELDS)."""
-        s = self._f64(self.batch, TICK_STATE)
-        check(lib().qloco_nlp_tick_get_state(self.batch, ptr(self.tick_workspace), ptr(s), self._stream(stream)),
-              "qloco_nlp_tick_get_state")
-        return s
+        return self._record("qloco_nlp_tick_get_state", self.tick_workspace, self._f64(self.batch, TICK_STATE), stream)
 
     def set_tick_state(self, state, stream=None):
-        _dev(state, "f64", (self.batch, TICK_STATE), "state")
-        check(lib().qloco_nlp_tick_set_state(self.batch, ptr(self.tick_workspace), ptr(state), self._stream(stream)),
-              "qloco_nlp_tick_set_state")
+        self._record("qloco_nlp_tick_set_state", self.tick_workspace,
+                     _dev(state, "f64", (self.batch, TICK_STATE), "state"), stream)
 
 
 NODE_STATE = 254      # QLOCO_NLP_NODE_STATE
@@ -257,13 +259,7 @@ GAIT_MSG_LEN, NRT_MSG_LEN = 100, 25
 def default_node_params(**overrides):
     """NLPRTControlClass.h:16-18, NLPClass.h:37-38, RobotPara_totalmass and
     the "go1" _rad."""
-    p = NlpNodeParams()
-    lib().qloco_nlp_node_params_default(C.byref(p))
-    for k, v in overrides.items():
-        if k == "reserved" or not hasattr(p, k):
-            raise ValueError("unknown parameter %s" % k)
-        setattr(p, k, v)
-    return p
+    return _defaults(NlpNodeParams, "nlp_node_params_default", overrides)
 
 
 @dataclass
@@ -282,22 +278,14 @@ class PlannerNode(PlannerTick):
 
     def __init__(self, batch, device, params=None, tick_params=None, node_params=None, steplength=0.075,
                  stepwidth=None, stepheight=None, **overrides):
-        import torch
         self.node_params = node_params if node_params is not None else default_node_params()
-        nbytes = lib().qloco_nlp_node_workspace_bytes(int(batch))
-        if nbytes <= 0:
-            raise ValueError("qloco_nlp_node_workspace_bytes(%d) = %d" % (batch, nbytes))
-        self.node_workspace = torch.zeros(nbytes // 8, dtype=torch.float64, device=torch.device(device))
+        self.node_workspace = _workspace("nlp_node_workspace_bytes", batch, device)
         super().__init__(batch, device, params=params, tick_params=tick_params, steplength=steplength,
                          stepwidth=stepwidth, stepheight=stepheight, **overrides)
 
     def init(self, steplength, stepwidth, stepheight=None, stream=None):
         """FootStepInputs + Initialize + NLPRTControlClass() of all three records."""
-        sl = self._per_robot(steplength, "steplength")
-        sw = self._per_robot(stepwidth, "stepwidth")
-        if stepheight is None:
-            stepheight = self._stepheight
-        sh = None if stepheight is None else self._per_robot(stepheight, "stepheight")
+        sl, sw, sh = self._step_inputs(steplength, stepwidth, stepheight)
         check(lib().qloco_nlp_node_init(C.byref(self.params), C.byref(self.tick_params), C.byref(self.node_params),
                                         self.batch, ptr(self.workspace), ptr(self.tick_workspace),
                                         ptr(self.node_workspace), ptr(sl), ptr(sw),
@@ -312,13 +300,10 @@ class PlannerNode(PlannerTick):
         """One iteration of the node loop: nrt_msg (B, 25), the latest
         /rt2nrt/state row of every robot (a device tensor; `qloco_rt_tick`'s
         output as it is).  out: a PlannerNodeResult of an earlier call."""
-        import torch
         B = self.batch
         _dev(nrt_msg, "f64", (B, NRT_MSG_LEN), "nrt_msg")
         if out is None:
-            out = PlannerNodeResult(self._f64(B, GAIT_MSG_LEN),
-                                    torch.empty((B, NODE_SCHED_LEN), dtype=torch.int32, device=self.device),
-                                    torch.empty((B,), dtype=torch.int32, device=self.device))
+            out = PlannerNodeResult(self._f64(B, GAIT_MSG_LEN), self._i32(B, NODE_SCHED_LEN), self._i32(B))
         check(lib().qloco_nlp_node_tick(
             C.byref(self.params), C.byref(self.tick_params), C.byref(self.node_params), B, ptr(self.workspace),
             ptr(self.tick_workspace), ptr(self.node_workspace), ptr(nrt_msg), ptr(out.gait_msg), ptr(out.sched),
@@ -343,15 +328,11 @@ class PlannerNode(PlannerTick):
 
     def get_node_state(self, stream=None):
         """Dense (B, 254) node record per robot (NODE_STATE_FIELDS)."""
-        s = self._f64(self.batch, NODE_STATE)
-        check(lib().qloco_nlp_node_get_state(self.batch, ptr(self.node_workspace), ptr(s), self._stream(stream)),
-              "qloco_nlp_node_get_state")
-        return s
+        return self._record("qloco_nlp_node_get_state", self.node_workspace, self._f64(self.batch, NODE_STATE), stream)
 
     def set_node_state(self, state, stream=None):
-        _dev(state, "f64", (self.batch, NODE_STATE), "state")
-        check(lib().qloco_nlp_node_set_state(self.batch, ptr(self.node_workspace), ptr(state), self._stream(stream)),
-              "qloco_nlp_node_set_state")
+        self._record("qloco_nlp_node_set_state", self.node_workspace,
+                     _dev(state, "f64", (self.batch, NODE_STATE), "state"), stream)
 
 
 def set_node_form(form):
