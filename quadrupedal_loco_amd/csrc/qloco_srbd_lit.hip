@@ -57,30 +57,29 @@ struct LitLds {
   // loops is a compile-time constant plus the wave's offset
   static constexpr int NS = W == 1 ? kLitN : kLitN2;
   static constexpr int NT = NS;
+  // Member order: the ADMM iteration addresses LDS from a few
+  // loop-invariant lane registers, and the two-address reads reach 255 dwords
+  // (ds_read2_b32) or 255 x 256 B (ds_read2st64_b32) from them.  The small
+  // constant tables come first (768 B for one wave, padded to 1024 B for two:
+  // the Bb columns within a ds_read2_b32 of 4 (lane % 12)), and every per-lane
+  // array of the loop, the union's w0i included, then starts a multiple of
+  // 256 B after bc: one register 4 lane serves them all with immediate offsets.
+  float Bb[6][12];          // wrench map (constant feet), rows omega 0..2, v 3..5 (rows read as f4v)
+  float Te[6][6];           // dt^2 blockdiag(Rz' Qtheta Rz, Qp)
+  float q2[16], r2[12], x0[16];
+  float ctf[4 * NT];        // contact flags as floats
+  float pad0[W == 1 ? 0 : 24];
   f4v bc[W][W][16];         // broadcast rows: 60-vectors read as one 16-B chunk per lane, [parity][half]
                             // (one wave: its LDS ops run in order, so one buffer serves every reuse;
                             // two waves: double-buffered by iteration / pivot parity, one barrier each)
   float av[W][2][64];       // per wave, per slot exchange (a, D x, t)
   float wv[W][64];          // per wave, wrench rows (s, w)
-  f2v k0k2[NT][NT];         // horizon sums K0 / K2 (row step, column step; column-space steps)
-  float Bb[6][12];          // wrench map (constant feet), rows omega 0..2, v 3..5
-  float Te[6][6];           // dt^2 blockdiag(Rz' Qtheta Rz, Qp)
-  float q2[16], r2[12], x0[16];
-  float ctf[4 * NT];        // contact flags as floats
-  f4v arz[W][2][64];        // per slot: scaled A entries (ra0, ra1, rz0, rz1)
   float zh[W][2][64];       // per slot: row 0's scaled upper bound (x / y rows: inf); the lower
                             // bound is 0 (x / y) or zh fz_min / fz_max (z rows)
   float dr[W][2][64];       // per slot: the Ruiz column scale D (read where needed: not a
                             // register live across the ADMM loop)
   float qvl[W][2][64];      // per slot: the scaled gradient q~ (read where needed)
-  // block-uniform solver state, one copy per wave (both waves take identical
-  // decisions): read into SGPRs where a phase needs it, so no register carries
-  // it across the ADMM iterations
-  struct {
-    float rho, cs, cinv, qn0, qn1, alpha, oma, sigma, dtm;
-    float sxy[2][2];  // S of the omega x / y block: G^-1 = sum_a S[.][a] A_a^-1 S[.][a] (see the G^-1 tables)
-    int iter, status, rho_updates, ctm, interval;
-  } sc[W];
+  f4v arz[W][2][64];        // per slot: scaled A entries (ra0, ra1, rz0, rz1)
   union alignas(16) {       // phase-local storage (LDS bounds the one-wave occupancy: <= 10 KB;
                             // 16-byte aligned: dcol is read as f4v, a misaligned ds_read_b128
                             // cost the one-wave kernel 46 us per launch)
@@ -91,11 +90,23 @@ struct LitLds {
       float Wc[12 * NT];
     };
     struct {                // factorisation
-      float w0i[W][3][2][64];   // per variable its row of W0^-1 (x, y, z), read by the U rows
+      float w0i[W][3][2][64];   // per variable its row of W0^-1 (x, y, z), read by the U rows; between
+                                // two factorisations the ADMM segments park D^-1 in [0] and the
+                                // first rows' lower bound in [1]
       f2v gtab[NT][NT][3];      // G^-1 blocks: per (row step, column step) in
                                 // column-space order, (W0, W1), (W2, V0), (V1, V2)
     };
   };
+  f2v k0k2[NT][NT];         // horizon sums K0 / K2 (row step, column step; column-space steps)
+  // block-uniform solver state, one copy per wave (both waves take identical
+  // decisions): read into SGPRs where a phase needs it, so no register carries
+  // it across the ADMM iterations
+  struct {
+    float rho, cs, cinv, qn0, qn1, alpha, oma, sigma, dtm;
+    float zlo;        // fz_min / fz_max: the z rows' lower bound is zlo times the upper one
+    float sxy[2][2];  // S of the omega x / y block: G^-1 = sum_a S[.][a] A_a^-1 S[.][a] (see the G^-1 tables)
+    int iter, status, rho_updates, ctm, interval;
+  } sc[W];
   float piv[W == 1 ? 0 : 2];       // two waves: the Gauss-Jordan pivot, [parity]
   float red[W == 1 ? 0 : 2][16];   // two waves: per-wave partials of the block reductions
 };
@@ -103,6 +114,12 @@ static_assert(sizeof(LitLds<1>) <= 10240, "literal kernel: four workgroups per S
 static_assert(sizeof(LitLds<2>) <= 40960, "two-wave literal kernel: four workgroups per CU need <= 40 KB");
 static_assert(offsetof(LitLds<1>, dcol) % 16 == 0 && offsetof(LitLds<2>, dcol) % 16 == 0,
               "dcol is read as f4v (ds_read_b128 needs 16-byte alignment)");
+static_assert(offsetof(LitLds<1>, Bb) % 16 == 0 && offsetof(LitLds<1>, bc) % 16 == 0 && offsetof(LitLds<1>, arz) % 16 == 0 &&
+                  offsetof(LitLds<2>, Bb) % 16 == 0 && offsetof(LitLds<2>, bc) % 16 == 0 && offsetof(LitLds<2>, arz) % 16 == 0,
+              "Bb rows, bc and arz are read as f4v");
+static_assert((offsetof(LitLds<1>, w0i) - offsetof(LitLds<1>, bc)) % 256 == 0 &&
+                  (offsetof(LitLds<2>, w0i) - offsetof(LitLds<2>, bc)) % 256 == 0 && offsetof(LitLds<1>, Bb) == 0,
+              "the ADMM loop's two-address reads reach its per-lane arrays from one lane register");
 
 // Wave-level helpers for the one-wave literal kernel
 __device__ __forceinline__ void lsync() {
@@ -249,7 +266,7 @@ __device__ __forceinline__ void lit_invert(LitLds<1> &S, int lane, int ncol, Row
     const float v = K.k[k];
     const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
     const float pinv = __builtin_amdgcn_rcpf(p);
-    const float ng = -(is_k ? (1.0f - pinv) : v * pinv);
+    const float ng = is_k ? pinv - 1.0f : -v * pinv;  // -(1 - pinv), -(v pinv): the same bits, no sign flip after the select
     if constexpr (k + 1 < 60) {  // unconditional (harmless past the last pivot): no branch to join
       const bool is_k1 = __builtin_amdgcn_inverse_ballot_w64(1ull << (k + 1));
       const bool upto_k = __builtin_amdgcn_inverse_ballot_w64((2ull << k) - 1ull);
@@ -257,7 +274,9 @@ __device__ __forceinline__ void lit_invert(LitLds<1> &S, int lane, int ncol, Row
       const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, la), k + 1));
       reinterpret_cast<float *>(&S.bc[0][0][0])[lane] = is_k1 ? p1 + 1.0f : (upto_k ? -la : la);
     }
-    QL_DPP_GJ60(K.k, 0, r0, ng);
+    // (the _P1 block opens with s_nop 1, not 4: r0 comes straight from the ds_read and this
+    // function's control flow is scalar, so no VALU write of EXEC precedes the DPP)
+    QL_DPP_GJ60_P1(K.k, 0, r0, ng);
     if (p > kGjExactPivot) K.k[k] = is_k ? pinv : ng;
   });
   lsync();
@@ -304,7 +323,7 @@ __device__ __forceinline__ void lit2_pivot(LitLds<2> &S, int wv, int nc, Row<2> 
     const float v = K.k[k];
     const float pinv = __builtin_amdgcn_rcpf(p);
     const bool own = wv == HF && tt == KL;
-    const float ng = -(own ? (1.0f - pinv) : v * pinv);
+    const float ng = own ? pinv - 1.0f : -v * pinv;
     if constexpr (KL >= 1) {  // look-ahead: the next pivot is column k - 1 of this half
       const float la = fmaf(dpp_col<KL - 1>(HF ? r1 : r0), ng, K.k[k - 1]);
       const bool own1 = wv == HF && tt == KL - 1;
@@ -802,6 +821,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
     S.sc[wv].oma = 1.0f - a.alpha;
     S.sc[wv].sigma = a.sigma;
     S.sc[wv].dtm = dtm;
+    S.sc[wv].zlo = a.fz_max > 0.0f ? a.fz_min / a.fz_max : 0.0f;
     const int ctm = a.check_termination;
     S.sc[wv].ctm = ctm;
     S.sc[wv].interval = (a.adaptive_rho && a.rho_interval == 0) ? (ctm ? 4 * ctm : 100)
@@ -1277,7 +1297,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         const float rho = uf(S.sc[wv].rho);
         const float rho_s = rho;
         const float rvb_s = sgpr_f(1.0f / rho);
-        const float zlo = a.fz_max > 0.0f ? a.fz_min / a.fz_max : 0.0f;  // z rows: lower = zlo upper
+        const float zlo = uf(S.sc[wv].zlo);  // z rows: lower = zlo upper (from LDS: no register across the phases)
         QL_LIT_LANE_INDICES(lxi);
         // loop operands read here, per segment of iterations: none is a register
         // across the residual checks and factorisations
@@ -1293,6 +1313,10 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           qvr[h] = S.qvl[wv][h][lxi];
           Dinv[h] = valid[h] ? 1.0f / S.dr[wv][h][lxi] : 0.0f;
           S.w0i[wv][0][h][lxi] = Dinv[h];
+          // the first row's lower bound (0 on x / y rows, zlo zh on z rows) is
+          // constant for the solve: parked beside D^-1 and read next to zh, so
+          // neither a multiply and a select per iteration nor a loop register
+          S.w0i[wv][1][h][lxi] = xy ? 0.0f : zlo * S.zh[wv][h][lxi];
         }
         // rho vector (eq rows 1e3 rho) of the slots' first rows and its inverse,
         // held for the segment (four registers; the second rows' rho is the scalar)
@@ -1417,7 +1441,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           // variable's omega rows of B_d (a padding slot's are harmless: its
           // leg's W0^-1 coefficients are zero), a and D^-1
           float sv;
-          float bw0, bw1, bw2, zhi[2], avr[2];
+          float bw0, bw1, bw2, zhi[2], zlw[2], avr[2];
           {
             const f4v r0 = S.bc[par][0][lxi & 15];
             f4v r1;
@@ -1443,22 +1467,28 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
           lsync();
           // x~ = D^-1 a - D^-1 W0^-1 Vu' s, then update_x / update_z / update_y:
           // both slots' wrench triples under one wait, the chains side by side
-          f2v s01[2], s23[2], s45[2];
+          // (the step's omega rows and the variable's own v row, the latter by
+          // its lane address: no select.  Slot 1's step is slot 0's + 5, so one
+          // pair of address registers serves both slots; a padding slot 1 reads
+          // finite values that its zero W0^-1 coefficients drop.)
+          f2v s01[2];
+          float s2[2], sf[2];
+          {
+            const float *gs = &S.wv[wv][6 * stepl[0]], *gc = gs + 3 + comp;
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const float *gs = &S.wv[wv][6 * stepl[h]];
-            s01[h] = *reinterpret_cast<const f2v *>(gs);
-            s23[h] = *reinterpret_cast<const f2v *>(gs + 2);
-            s45[h] = *reinterpret_cast<const f2v *>(gs + 4);
+            for (int h = 0; h < 2; ++h) sf[h] = gc[30 * h];  // issued in the order the sums below take them
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) s2[h] = gs[30 * h + 2];
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) s01[h] = *reinterpret_cast<const f2v *>(gs + 30 * h);
+            __builtin_amdgcn_sched_barrier(0);
           }
-          asm volatile("" : "+v"(s45[0]), "+v"(s45[1]));  // loaded by every lane (no exec-masked load)
           float tv[2], td[2];
 #pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            const float f0 = s23[h].y, f1 = s45[h].x, f2 = s45[h].y;
-            const float sf = comp == 0 ? f0 : (comp == 1 ? f1 : f2);
-            tv[h] = fmaf(bw0, s01[h].x, fmaf(bw1, s01[h].y, fmaf(bw2, s23[h].x, dtm * sf)));
-          }
+          for (int h = 0; h < 2; ++h)
+            tv[h] = fmaf(bw0, s01[h].x, fmaf(bw1, s01[h].y, fmaf(bw2, s2[h], dtm * sf[h])));
           // (ra, rz) for update_z and the next iteration's rhs: into the registers
           // the wrench triples leave, under the two W0^-1 products
           asm volatile("" : "+v"(tv[0]), "+v"(tv[1]));
@@ -1470,25 +1500,42 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
             zhi[h] = S.zh[wv][h][lxi];
+            zlw[h] = S.w0i[wv][1][h][lxi];
             qvr[h] = S.qvl[wv][h][lxi];
           }
+          // (stage by stage over the two slots, like the chains above: a packed
+          // result is not the next instruction's operand)
+          float xt[2], xtz[2];
+          f2v zt[2], zr[2], vv[2], zn[2];
+#pragma unroll
+          for (int h = 0; h < 2; ++h) xt[h] = Dinv[h] * (avr[h] - td[h]);  // D^-1 (a - W0^-1 t)
 #pragma unroll
           for (int h = 0; h < 2; ++h) {
-            const float xt = Dinv[h] * (avr[h] - td[h]);  // D^-1 (a - W0^-1 t)
+            const float n1 = lane_next(xt[h]), n2 = lane_next(n1);
+            xtz[h] = comp == 0 ? n2 : n1;
+            x[h] = fmaf(alpha, xt[h], oma * x[h]);
+          }
+          asm volatile("" : "+v"(arzc[0]), "+v"(arzc[1]));  // both quads under one wait
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
             const f2v ra = {arzc[h].x, arzc[h].y}, rz = {arzc[h].z, arzc[h].w};
-            const float hi = zhi[h];
-            const f2v bnd = {xy ? 0.0f : zlo * hi, hi};
-            const float n1 = lane_next(xt), n2 = lane_next(n1);
-            const float xtz = comp == 0 ? n2 : n1;
-            x[h] = fmaf(alpha, xt, oma * x[h]);
-            const f2v rv = {rva[h][0], rva[h][1]};
+            zt[h] = __builtin_elementwise_fma(rz, (f2v)(xtz[h]), ra * xt[h]);
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h) zr[h] = __builtin_elementwise_fma((f2v)(alpha), zt[h], oma * z[h]);
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
             const f2v rvi2 = {rvia[h], rvb};
-            const f2v zt = __builtin_elementwise_fma(rz, (f2v)(xtz), ra * xt);
-            const f2v zr = __builtin_elementwise_fma((f2v)(alpha), zt, oma * z[h]);
-            const f2v v = __builtin_elementwise_fma(y[h], rvi2, zr);
-            const f2v zn = {__builtin_amdgcn_fmed3f(v.x, bnd.x, bnd.y), __builtin_amdgcn_fmed3f(v.y, -INFINITY, 0.0f)};
-            y[h] = __builtin_elementwise_fma(rv, zr - zn, y[h]);
-            z[h] = zn;
+            vv[h] = __builtin_elementwise_fma(y[h], rvi2, zr[h]);
+          }
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            zn[h] = {__builtin_amdgcn_fmed3f(vv[h].x, zlw[h], zhi[h]), __builtin_amdgcn_fmed3f(vv[h].y, -INFINITY, 0.0f)};
+#pragma unroll
+          for (int h = 0; h < 2; ++h) {
+            const f2v rv = {rva[h][0], rva[h][1]};
+            y[h] = __builtin_elementwise_fma(rv, zr[h] - zn[h], y[h]);
+            z[h] = zn[h];
           }
         }
       }

@@ -45,14 +45,17 @@ def matvec(acc, nch=16):
             "\\n\\t\" \\\n      \"".join(body) + "\" \\\n      : " + outs + " \\\n      : " + ins + ")\n")
 
 
-def gj(nch=16):
+def gj(nch=16, pad=4):
     # outputs KK[B+c] = %c (c < 4 nch), inputs R.x..R.w = %nc..%nc+3, NG = %nc+4
+    # pad = 1 (the _P1 form): for callers whose R comes straight from a ds_read
+    # and that have no VALU write of EXEC before the block -- as in the matvec
+    # forms, s_nop 1 then covers a compiler-inserted copy of R
     nc = 4 * nch
-    body = ["s_nop 4"] + [dpp(4 * j + e, nc + e, nc + 4, j) for j in range(nch) for e in range(4)]
+    body = ["s_nop %d" % pad] + [dpp(4 * j + e, nc + e, nc + 4, j) for j in range(nch) for e in range(4)]
     outs = ", ".join('"+v"((KK)[(B) + %d])' % c for c in range(nc))
     ins = '"v"((R).x), "v"((R).y), "v"((R).z), "v"((R).w), "v"(NG)'
     return ("// KK[B + 4j + e] += R_e(lane j of the row) * NG, columns < %d\n" % nc +
-            "#define QL_DPP_GJ%d(KK, B, R, NG) \\\n  asm(\"" % nc +
+            "#define QL_DPP_GJ%d%s(KK, B, R, NG) \\\n  asm(\"" % (nc, "" if pad == 4 else "_P%d" % pad) +
             "\\n\\t\" \\\n      \"".join(body) + "\" \\\n      : " + outs + " \\\n      : " + ins + ")\n")
 
 
@@ -124,5 +127,7 @@ if __name__ == "__main__":
                 # W = 2 second-half forms for the narrow buckets (<= 12 / <= 24
                 # columns: 22-25 / 26-29 stance legs, the mixed schedules)
                 matvec(True, 3) + "\n" + matvec(True, 6) + "\n" + gj(3) + "\n" + gj(6) + "\n" +
-                mul(3) + "\n" + mul(6) + "\n" + absmax(3) + "\n" + absmax(6))
+                mul(3) + "\n" + mul(6) + "\n" + absmax(3) + "\n" + absmax(6) + "\n" +
+                # the one-wave literal inverse's pivot update
+                gj(15, 1))
     print(OUT)
