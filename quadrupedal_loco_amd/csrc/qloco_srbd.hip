@@ -47,6 +47,7 @@
 
 #include "qloco_common.hpp"
 #include "qloco_srbd_core.hpp"
+#include "qloco_srbd_model.hpp"
 #include "qloco_srbd_tables.hpp"
 
 // The KKT inverse is the register-row DPP Gauss-Jordan below.  The
@@ -56,7 +57,6 @@
 
 namespace qloco {
 
-constexpr int kMaxN = 20;    // max horizon compiled in (BASELINE configs: N <= 20)
 constexpr int kLegsPerWave = 21;
 // The one-wave class takes instances of at most kW1Legs stance legs.  20
 // (60 variables, every Go1 trot / pace N = 10 instance) lets the one-wave
@@ -569,71 +569,23 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   const float dtm = dt / a.mass, dt2m = dt * dt / a.mass;
 
   // ---------------- 1. inputs -> LDS (one instance per block)
-  if (t < 13) S.x0[t] = a.x0[b * 13 + t];
-  if (t == 0) {  // static indices: kernel-argument arrays never indexed per lane
-#pragma unroll
-    for (int k = 0; k < 13; ++k) S.q2[k] = a.q2[k];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) S.r2[k] = a.r2[k];
-  }
-  {
-    const int nct = a.contacts_per_step ? 4 * N : 4;
-    for (int k = t; k < 4 * N; k += NC)
-      S.ct[k] = a.contacts[b * nct + (a.contacts_per_step ? k : (k & 3))] ? 1 : 0;
-  }
+  srbd_load_inputs<NC>(a, S, b, t);
   bsync<W>();
 
-  // ---------------- 2. variable enumeration (integer, bit-exact): the stance
-  // (step, leg) pairs, or every pair for the literal full QP
-  if (wave == 0) {
-    const bool s0 = (lane < 4 * N) && (a.literal || S.ct[lane]);
-    const bool s1 = (64 + lane < 4 * N) && (a.literal || S.ct[64 + lane]);
-    const uint64_t m0 = __ballot(s0), m1 = __ballot(s1);
-    const uint64_t below = (1ull << lane) - 1ull;
-    const int c0 = __popcll(m0);
-    if (s0) S.legtab[__popcll(m0 & below)] = lane;
-    if (s1) S.legtab[c0 + __popcll(m1 & below)] = 64 + lane;
-    if (lane == 0) S.nlegs = c0 + __popcll(m1);
-    if (lane <= N) {
-      const int q = 4 * lane;
-      const uint64_t l0 = q >= 64 ? ~0ull : ((1ull << q) - 1ull);
-      const int q1 = q - 64;
-      const uint64_t l1 = q1 <= 0 ? 0ull : ((1ull << q1) - 1ull);
-      S.stepstart[lane] = __popcll(m0 & l0) + __popcll(m1 & l1);
-    }
-  }
+  // ---------------- 2. variable enumeration: the stance (step, leg) pairs, or
+  // every pair for the literal full QP
+  srbd_enumerate_stance(a, S, t);
   bsync<W>();
   const int nlegs = uni(S.nlegs);
   const int n = 3 * nlegs;
   if (nlegs < a.leg_lo || nlegs > a.leg_hi) return;  // the other launch's instance
-  if (nlegs > (W == 1 ? kW1Legs : w2_bucket_legs(C2))) {  // uniform: the caller's max_stance_legs was too small
-    if (t < 12) a.u0[b * 12 + t] = NAN;
-    if (a.u)
-      for (int k = t; k < 12 * N; k += NC) a.u[b * 12 * N + k] = NAN;
-    if (t == 0) {
-      if (a.status) a.status[b] = QLOCO_BAD_SIZE;
-      if (a.iters) a.iters[b] = 0;
-      if (a.rho_updates) a.rho_updates[b] = 0;
-      if (a.obj) a.obj[b] = NAN;
-    }
+  if (nlegs > (W == 1 ? kW1Legs : w2_bucket_legs(C2))) {  // uniform
+    srbd_refuse_bad_size<NC>(a, b, t);
     return;
   }
-  // persistent solver (warm_start == 2, A1RobotControl.cpp:556-578): the
-  // record of this instance's last call (layout: QLOCO_SRBD_PERSIST_LEN)
   const int NP = 100 * N;
-  float *prec = (WS && a.warm_start == 2) ? a.warm + b * (int64_t)(NP + 4) : nullptr;
-  bool p_init = false, p_same = false;
-  if (prec) {
-    p_init = prec[NP + 1] > 0.5f;
-    // literal full QP: the problem structure never changes (the reference's
-    // Hessian pattern is contact-independent, ConvexMpc.cpp:211-215), so
-    // every call after the first takes the update path; the stance-only
-    // reduction re-initialises when its variable set changes
-    int mism = 0;
-    if (!a.literal)
-      for (int k = t; k < 4 * N; k += 64 * W) mism |= (prec[96 * N + k] != 0.0f) != (S.ct[k] != 0);
-    p_same = p_init && !__syncthreads_or(mism);
-  }
+  bool p_init, p_same;
+  float *prec = srbd_persist_record<NC, WS>(a, S, b, t, p_init, p_same);
   // valid columns per wave, from the stance-leg count (re-read from LDS at
   // each factorisation rather than kept live across the ADMM loop)
   auto col_counts = [&](int nl, int (&ncol)[W]) {
@@ -665,49 +617,11 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   const float R00 = cy, R01 = sy, R10 = -sy, R11 = cy;
   f4v lo, hi;
   {
-    float Ii[3][3];
-    const float *I = a.inertia;
-    const float Rm[3][3] = {{R00, R01, 0.f}, {R10, R11, 0.f}, {0.f, 0.f, 1.f}};
-    float RI[3][3], Iw[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        RI[r][c] = Rm[r][0] * I[c * 3 + 0] + Rm[r][1] * I[c * 3 + 1] + Rm[r][2] * I[c * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        Iw[r][c] = RI[r][0] * Rm[c][0] + RI[r][1] * Rm[c][1] + RI[r][2] * Rm[c][2];
-    const float c00 = Iw[1][1] * Iw[2][2] - Iw[1][2] * Iw[2][1];
-    const float c01 = Iw[1][2] * Iw[2][0] - Iw[1][0] * Iw[2][2];
-    const float c02 = Iw[1][0] * Iw[2][1] - Iw[1][1] * Iw[2][0];
-    const float id = 1.0f / (Iw[0][0] * c00 + Iw[0][1] * c01 + Iw[0][2] * c02);
-    Ii[0][0] = c00 * id;
-    Ii[1][0] = c01 * id;
-    Ii[2][0] = c02 * id;
-    Ii[0][1] = (Iw[0][2] * Iw[2][1] - Iw[0][1] * Iw[2][2]) * id;
-    Ii[1][1] = (Iw[0][0] * Iw[2][2] - Iw[0][2] * Iw[2][0]) * id;
-    Ii[2][1] = (Iw[0][1] * Iw[2][0] - Iw[0][0] * Iw[2][1]) * id;
-    Ii[0][2] = (Iw[0][1] * Iw[1][2] - Iw[0][2] * Iw[1][1]) * id;
-    Ii[1][2] = (Iw[0][2] * Iw[1][0] - Iw[0][0] * Iw[1][2]) * id;
-    Ii[2][2] = (Iw[0][0] * Iw[1][1] - Iw[0][1] * Iw[1][0]) * id;
+    float Ii[3][3], ba[3];
+    srbd_inertia_inv(cy, sy, a.inertia, Ii);
     // this lane's B_d column (rows 6..8) and E = dt A_c B_d column (rows 0..2)
-    const float *rf = a.feet + b * (a.feet_per_step ? 12 * N : 12) +
-                      (a.feet_per_step ? 12 * step : 0) + 3 * leg;
-    const float rx = rf[0], ry = rf[1], rz = rf[2];
-    const float tv0 = comp == 0 ? 0.f : (comp == 1 ? -rz : ry);  // skew(r) e_comp (Utils.cpp:35-41)
-    const float tv1 = comp == 0 ? rz : (comp == 1 ? 0.f : -rx);
-    const float tv2 = comp == 0 ? -ry : (comp == 1 ? rx : 0.f);
-    float ba[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) ba[r] = dt * (Ii[r][0] * tv0 + Ii[r][1] * tv1 + Ii[r][2] * tv2);
-    lo = (f4v){ba[0], ba[1], ba[2], dt * (R00 * ba[0] + R01 * ba[1])};
-    hi = (f4v){dt * (R10 * ba[0] + R11 * ba[1]), dt * ba[2], (float)step, (float)comp};
-    if (!valid) {
-      lo = (f4v)(0.0f);
-      hi = (f4v){0.0f, 0.0f, 0.0f, -1.0f};
-    }
+    srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, step, leg), comp, dt, R00, R01,
+                   R10, R11, step, valid, ba, lo, hi);
     S.bv[t][0] = lo;
     S.bv[t][1] = hi;
   }
@@ -717,20 +631,7 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   //     free response A_d^{i+1} x0 in closed form (A_c nilpotent)
   for (int idx = t; idx < 12 * N; idx += NC) {
     const int i = idx / 12, s = idx - 12 * i;
-    const float k = (float)(i + 1);
-    const float *x0 = S.x0;
-    float xf;
-    if (s < 3) {
-      const float rw = s == 0 ? (R00 * x0[6] + R01 * x0[7]) : (s == 1 ? (R10 * x0[6] + R11 * x0[7]) : x0[8]);
-      xf = x0[s] + k * dt * rw;
-    } else if (s < 6) {
-      xf = x0[s] + k * dt * x0[s + 6];
-      if (s == 5) xf += 0.5f * k * (k - 1.0f) * dt * dt * x0[12];
-    } else if (s < 9) {
-      xf = x0[s];
-    } else {
-      xf = x0[s] + (s == 11 ? k * dt * x0[12] : 0.0f);
-    }
+    const float xf = srbd_free_state<12>(S.x0, s, i, dt, R00, R01, R10, R11);
     S.err[idx] = S.q2[s] * (xf - a.xref[b * 13 * N + 13 * i + s]);
   }
   // rows past the horizon stay zero for good (horizon_rows reads them)
@@ -1519,10 +1420,7 @@ extern "C" int qloco_srbd_route(const qloco_srbd_spec *spec) {
   if (!spec || spec->horizon < 1 || spec->horizon > kMaxN) return QLOCO_ERR_ARG;
   SrbdArgs a;
   memset(&a, 0, sizeof(a));
-  a.N = spec->horizon;
-  a.feet_per_step = spec->feet_per_step;
-  a.literal = spec->literal_full_qp ? 1 : 0;
-  for (int k = 0; k < 13; ++k) a.q2[k] = 2.0f * spec->q_weights[k];
+  srbd_args_from_spec(spec, &a);
   return srbd_route_of(a);
 }
 
@@ -1546,31 +1444,7 @@ extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, c
   if (spec->literal_full_qp < 0 || spec->literal_full_qp > 1) return QLOCO_ERR_ARG;
   SrbdArgs a;
   memset(&a, 0, sizeof(a));
-  a.N = spec->horizon;
-  a.feet_per_step = spec->feet_per_step;
-  a.contacts_per_step = spec->contacts_per_step;
-  a.output_frame = spec->output_frame;
-  a.dt = spec->dt;
-  a.mass = spec->mass;
-  for (int k = 0; k < 9; ++k) a.inertia[k] = spec->inertia[k];
-  for (int k = 0; k < 13; ++k) a.q2[k] = 2.0f * spec->q_weights[k];
-  for (int k = 0; k < 12; ++k) a.r2[k] = 2.0f * spec->r_weights[k];
-  a.mu = spec->mu;
-  a.fz_min = spec->fz_min;
-  a.fz_max = spec->fz_max;
-  a.rho = spec->rho;
-  a.sigma = spec->sigma;
-  a.alpha = spec->alpha;
-  a.eps_abs = spec->eps_abs;
-  a.eps_rel = spec->eps_rel;
-  a.max_iter = spec->max_iter;
-  a.check_termination = spec->check_termination;
-  a.scaling = spec->scaling;
-  a.adaptive_rho = spec->adaptive_rho;
-  a.rho_interval = spec->adaptive_rho_interval;
-  a.rho_tol = spec->adaptive_rho_tolerance;
-  a.warm_start = spec->warm_start;
-  a.literal = spec->literal_full_qp ? 1 : 0;
+  srbd_args_from_spec(spec, &a);
   a.batch = batch;
   a.x0 = x0;
   a.xref = x_ref;

@@ -169,66 +169,21 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   const float dt = a.dt;
   const float dtm = dt / a.mass, dt2m = dt * dt / a.mass;
 
-  // ---------------- 1. inputs -> LDS
-  if (t < 13) S.x0[t] = a.x0[b * 13 + t];
-  if (t == 0) {
-#pragma unroll
-    for (int k = 0; k < 13; ++k) S.q2[k] = a.q2[k];
-#pragma unroll
-    for (int k = 0; k < 12; ++k) S.r2[k] = a.r2[k];
-  }
-  {
-    const int nct = a.contacts_per_step ? 4 * N : 4;
-    for (int k = t; k < 4 * N; k += kBigThreads)
-      S.ct[k] = a.contacts[b * nct + (a.contacts_per_step ? k : (k & 3))] ? 1 : 0;
-  }
+  // ---------------- 1. inputs -> LDS, 2. stance enumeration (srbd_solve_one)
+  srbd_load_inputs<kBigThreads>(a, S, b, t);
   __syncthreads();
-
-  // ---------------- 2. stance enumeration (integer, bit-exact)
-  if (wave == 0) {  // the stance pairs, or every pair for the literal full QP
-    const bool s0 = (lane < 4 * N) && (a.literal || S.ct[lane]);
-    const bool s1 = (64 + lane < 4 * N) && (a.literal || S.ct[64 + lane]);
-    const uint64_t m0 = __ballot(s0), m1 = __ballot(s1);
-    const uint64_t below = (1ull << lane) - 1ull;
-    const int c0 = __popcll(m0);
-    if (s0) S.legtab[__popcll(m0 & below)] = lane;
-    if (s1) S.legtab[c0 + __popcll(m1 & below)] = 64 + lane;
-    if (lane == 0) S.nlegs = c0 + __popcll(m1);
-    if (lane <= N) {
-      const int q = 4 * lane;
-      const uint64_t l0 = q >= 64 ? ~0ull : ((1ull << q) - 1ull);
-      const int q1 = q - 64;
-      const uint64_t l1 = q1 <= 0 ? 0ull : ((1ull << q1) - 1ull);
-      S.stepstart[lane] = __popcll(m0 & l0) + __popcll(m1 & l1);
-    }
-  }
+  srbd_enumerate_stance(a, S, t);
   __syncthreads();
   const int nlegs = uni(S.nlegs);
   const int n = 3 * nlegs;
   if (nlegs < a.leg_lo || nlegs > a.leg_hi) return;  // another launch's instance
-  if (nlegs > big_bucket_legs(HC)) {  // uniform: the caller's max_stance_legs was too small
-    if (t < 12) a.u0[b * 12 + t] = NAN;
-    if (a.u)
-      for (int k = t; k < 12 * N; k += kBigThreads) a.u[b * 12 * N + k] = NAN;
-    if (t == 0) {
-      if (a.status) a.status[b] = QLOCO_BAD_SIZE;
-      if (a.iters) a.iters[b] = 0;
-      if (a.rho_updates) a.rho_updates[b] = 0;
-      if (a.obj) a.obj[b] = NAN;
-    }
+  if (nlegs > big_bucket_legs(HC)) {  // uniform
+    srbd_refuse_bad_size<kBigThreads>(a, b, t);
     return;
   }
-
   const int NP = 100 * N;
-  float *prec = (WS && a.warm_start == 2) ? a.warm + b * (int64_t)(NP + 4) : nullptr;
-  bool p_init = false, p_same = false;
-  if (prec) {
-    p_init = prec[NP + 1] > 0.5f;
-    int mism = 0;  // literal full QP: always the update path (srbd_solve_one)
-    if (!a.literal)
-      for (int k = t; k < 4 * N; k += kBigThreads) mism |= (prec[96 * N + k] != 0.0f) != (S.ct[k] != 0);
-    p_same = p_init && !__syncthreads_or(mism);
-  }
+  bool p_init, p_same;
+  float *prec = srbd_persist_record<kBigThreads, WS>(a, S, b, t, p_init, p_same);
 
   // variable r = 3 * (stance pair pl) + comp; r < n <=> pl < nlegs
   const int pl = r / 3;
@@ -254,48 +209,10 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   const float R00 = cy, R01 = sy, R10 = -sy, R11 = cy;  // A1RobotControl.cpp:506-508
   f4v lo, hi;
   {
-    float Ii[3][3];
-    const float *I = a.inertia;
-    const float Rm[3][3] = {{R00, R01, 0.f}, {R10, R11, 0.f}, {0.f, 0.f, 1.f}};
-    float RI[3][3], Iw[3][3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        RI[i][c] = Rm[i][0] * I[c * 3 + 0] + Rm[i][1] * I[c * 3 + 1] + Rm[i][2] * I[c * 3 + 2];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        Iw[i][c] = RI[i][0] * Rm[c][0] + RI[i][1] * Rm[c][1] + RI[i][2] * Rm[c][2];
-    const float c00 = Iw[1][1] * Iw[2][2] - Iw[1][2] * Iw[2][1];
-    const float c01 = Iw[1][2] * Iw[2][0] - Iw[1][0] * Iw[2][2];
-    const float c02 = Iw[1][0] * Iw[2][1] - Iw[1][1] * Iw[2][0];
-    const float id = 1.0f / (Iw[0][0] * c00 + Iw[0][1] * c01 + Iw[0][2] * c02);
-    Ii[0][0] = c00 * id;
-    Ii[1][0] = c01 * id;
-    Ii[2][0] = c02 * id;
-    Ii[0][1] = (Iw[0][2] * Iw[2][1] - Iw[0][1] * Iw[2][2]) * id;
-    Ii[1][1] = (Iw[0][0] * Iw[2][2] - Iw[0][2] * Iw[2][0]) * id;
-    Ii[2][1] = (Iw[0][1] * Iw[2][0] - Iw[0][0] * Iw[2][1]) * id;
-    Ii[0][2] = (Iw[0][1] * Iw[1][2] - Iw[0][2] * Iw[1][1]) * id;
-    Ii[1][2] = (Iw[0][2] * Iw[1][0] - Iw[0][0] * Iw[1][2]) * id;
-    Ii[2][2] = (Iw[0][0] * Iw[1][1] - Iw[0][1] * Iw[1][0]) * id;
-    const float *rf = a.feet + b * (a.feet_per_step ? 12 * N : 12) +
-                      (a.feet_per_step ? 12 * step : 0) + 3 * leg;
-    const float rx = rf[0], ry = rf[1], rz = rf[2];
-    const float tv0 = comp == 0 ? 0.f : (comp == 1 ? -rz : ry);  // skew(r) e_comp (Utils.cpp:35-41)
-    const float tv1 = comp == 0 ? rz : (comp == 1 ? 0.f : -rx);
-    const float tv2 = comp == 0 ? -ry : (comp == 1 ? rx : 0.f);
-    float ba[3];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) ba[i] = dt * (Ii[i][0] * tv0 + Ii[i][1] * tv1 + Ii[i][2] * tv2);
-    lo = (f4v){ba[0], ba[1], ba[2], dt * (R00 * ba[0] + R01 * ba[1])};
-    hi = (f4v){dt * (R10 * ba[0] + R11 * ba[1]), dt * ba[2], (float)step, (float)comp};
-    if (!valid) {
-      lo = (f4v)(0.0f);
-      hi = (f4v){0.0f, 0.0f, 0.0f, -1.0f};
-    }
+    float Ii[3][3], ba[3];
+    srbd_inertia_inv(cy, sy, a.inertia, Ii);
+    srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, step, leg), comp, dt, R00, R01,
+                   R10, R11, step, valid, ba, lo, hi);
     if (h == 0) {
       S.bv[r][0] = lo;
       S.bv[r][1] = hi;
@@ -306,20 +223,7 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   // ---------------- 4. gradient g = Bqp' Q (Aqp x0 - x_ref) (ConvexMpc.cpp:219-221)
   for (int idx = t; idx < 12 * N; idx += kBigThreads) {
     const int i = idx / 12, s = idx - 12 * i;
-    const float k = (float)(i + 1);
-    const float *x0 = S.x0;
-    float xf;
-    if (s < 3) {
-      const float rw = s == 0 ? (R00 * x0[6] + R01 * x0[7]) : (s == 1 ? (R10 * x0[6] + R11 * x0[7]) : x0[8]);
-      xf = x0[s] + k * dt * rw;
-    } else if (s < 6) {
-      xf = x0[s] + k * dt * x0[s + 6];
-      if (s == 5) xf += 0.5f * k * (k - 1.0f) * dt * dt * x0[12];
-    } else if (s < 9) {
-      xf = x0[s];
-    } else {
-      xf = x0[s] + (s == 11 ? k * dt * x0[12] : 0.0f);
-    }
+    const float xf = srbd_free_state<12>(S.x0, s, i, dt, R00, R01, R10, R11);
     S.err[idx] = S.q2[s] * (xf - a.xref[b * 13 * N + 13 * i + s]);
   }
   __syncthreads();

@@ -14,10 +14,9 @@
 #include <string.h>
 
 #include "qloco_common.hpp"
+#include "qloco_srbd_model.hpp"
 
 namespace qloco {
-
-constexpr int kBuildMaxN = 20;
 
 struct BuildArgs {
   int N, feet_per_step, contacts_per_step;
@@ -31,12 +30,12 @@ struct BuildArgs {
 };
 
 __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
-  __shared__ float Bd[kBuildMaxN][6][12];  // rows 6..11 of B_d (rows 0..5 are zero)
-  __shared__ float Ed[kBuildMaxN][6][12];  // rows 0..5 of E = dt A_c B_d
+  __shared__ float Bd[kMaxN][6][12];  // rows 6..11 of B_d (rows 0..5 are zero)
+  __shared__ float Ed[kMaxN][6][12];  // rows 0..5 of E = dt A_c B_d
   __shared__ float q2[13];
   __shared__ float r2[12];
   __shared__ float x0[13];
-  __shared__ float werr[kBuildMaxN * 13];  // Q (Aqp x0 - x_ref)
+  __shared__ float werr[kMaxN * 13];  // Q (Aqp x0 - x_ref)
   const int t = threadIdx.x;
   const int64_t b = blockIdx.x;
   const int N = a.N, nx = 13 * N, nu = 12 * N, nc = 20 * N;
@@ -57,39 +56,11 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
   for (int idx = t; idx < N * 12; idx += 256) {
     const int k = idx / 12, col = idx - 12 * k;
     const int leg = col / 3, comp = col - 3 * leg;
-    float RI[3][3], Iw[3][3], Ii[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        RI[r][c] = Rm[r][0] * a.inertia[c * 3 + 0] + Rm[r][1] * a.inertia[c * 3 + 1] +
-                   Rm[r][2] * a.inertia[c * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        Iw[r][c] = RI[r][0] * Rm[c][0] + RI[r][1] * Rm[c][1] + RI[r][2] * Rm[c][2];
-    const float c00 = Iw[1][1] * Iw[2][2] - Iw[1][2] * Iw[2][1];
-    const float c01 = Iw[1][2] * Iw[2][0] - Iw[1][0] * Iw[2][2];
-    const float c02 = Iw[1][0] * Iw[2][1] - Iw[1][1] * Iw[2][0];
-    const float id = 1.0f / (Iw[0][0] * c00 + Iw[0][1] * c01 + Iw[0][2] * c02);
-    Ii[0][0] = c00 * id;
-    Ii[1][0] = c01 * id;
-    Ii[2][0] = c02 * id;
-    Ii[0][1] = (Iw[0][2] * Iw[2][1] - Iw[0][1] * Iw[2][2]) * id;
-    Ii[1][1] = (Iw[0][0] * Iw[2][2] - Iw[0][2] * Iw[2][0]) * id;
-    Ii[2][1] = (Iw[0][1] * Iw[2][0] - Iw[0][0] * Iw[2][1]) * id;
-    Ii[0][2] = (Iw[0][1] * Iw[1][2] - Iw[0][2] * Iw[1][1]) * id;
-    Ii[1][2] = (Iw[0][2] * Iw[1][0] - Iw[0][0] * Iw[1][2]) * id;
-    Ii[2][2] = (Iw[0][0] * Iw[1][1] - Iw[0][1] * Iw[1][0]) * id;
-    const float *rf = a.feet + b * (a.feet_per_step ? nu : 12) + (a.feet_per_step ? 12 * k : 0) + 3 * leg;
-    const float rx = rf[0], ry = rf[1], rz = rf[2];
-    const float tv0 = comp == 0 ? 0.f : (comp == 1 ? -rz : ry);  // skew(r) e_comp (Utils.cpp:35-41)
-    const float tv1 = comp == 0 ? rz : (comp == 1 ? 0.f : -rx);
-    const float tv2 = comp == 0 ? -ry : (comp == 1 ? rx : 0.f);
-    float w[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) w[r] = dt * (Ii[r][0] * tv0 + Ii[r][1] * tv1 + Ii[r][2] * tv2);
+    float Ii[3][3], w[3];
+    f4v lo, hi;  // lo = {w, E row 0}, hi = {E rows 1, 2, ..}
+    srbd_inertia_inv(cy, sy, a.inertia, Ii);
+    srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, k, leg), comp, dt, Rm[0][0],
+                   Rm[0][1], Rm[1][0], Rm[1][1], k, true, w, lo, hi);
     const float vm = dt / a.mass;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
@@ -97,30 +68,16 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
       Bd[k][3 + r][col] = (r == comp) ? vm : 0.0f;
     }
     // E = dt A_c B_d: rows 0..2 = dt Rz w, rows 3..5 = dt v-rows
-    Ed[k][0][col] = dt * (Rm[0][0] * w[0] + Rm[0][1] * w[1]);
-    Ed[k][1][col] = dt * (Rm[1][0] * w[0] + Rm[1][1] * w[1]);
-    Ed[k][2][col] = dt * w[2];
+    Ed[k][0][col] = lo.w;
+    Ed[k][1][col] = hi.x;
+    Ed[k][2][col] = hi.y;
 #pragma unroll
     for (int r = 0; r < 3; ++r) Ed[k][3 + r][col] = (r == comp) ? dt * vm : 0.0f;
   }
   // Q (A_qp x0 - x_ref), free response in closed form
   for (int idx = t; idx < nx; idx += 256) {
     const int i = idx / 13, s = idx - 13 * i;
-    const float k = (float)(i + 1);
-    float xf;
-    if (s < 3) {
-      const float rw = s == 0 ? (cy * x0[6] + sy * x0[7]) : (s == 1 ? (-sy * x0[6] + cy * x0[7]) : x0[8]);
-      xf = x0[s] + k * dt * rw;
-    } else if (s < 6) {
-      xf = x0[s] + k * dt * x0[s + 6];
-      if (s == 5) xf += 0.5f * k * (k - 1.0f) * dt * dt * x0[12];
-    } else if (s < 9) {
-      xf = x0[s];
-    } else if (s < 12) {
-      xf = x0[s] + (s == 11 ? k * dt * x0[12] : 0.0f);
-    } else {
-      xf = x0[12];
-    }
+    const float xf = srbd_free_state<13>(x0, s, i, dt, Rm[0][0], Rm[0][1], Rm[1][0], Rm[1][1]);
     werr[idx] = q2[s] * (xf - a.xref[b * nx + idx]);
   }
   __syncthreads();
@@ -213,7 +170,7 @@ extern "C" int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, cons
                                 float *H, float *g, float *lb, float *ub, float *Aqp, float *Bqp,
                                 void *stream) {
   if (!spec || batch < 0) return QLOCO_ERR_ARG;
-  if (spec->horizon < 1 || spec->horizon > kBuildMaxN) return QLOCO_BAD_SIZE;
+  if (spec->horizon < 1 || spec->horizon > kMaxN) return QLOCO_BAD_SIZE;
   if (batch == 0) return QLOCO_OK;
   if (!x0 || !x_ref || !feet) return QLOCO_ERR_ARG;
   if ((lb || ub) && (!lb || !ub || !contacts)) return QLOCO_ERR_ARG;
@@ -229,8 +186,7 @@ extern "C" int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, cons
   a.fz_min = spec->fz_min;
   a.fz_max = spec->fz_max;
   for (int k = 0; k < 9; ++k) a.inertia[k] = spec->inertia[k];
-  for (int k = 0; k < 13; ++k) a.q2[k] = 2.0f * spec->q_weights[k];
-  for (int k = 0; k < 12; ++k) a.r2[k] = 2.0f * spec->r_weights[k];
+  srbd_doubled_weights(spec, a.q2, a.r2);
   a.batch = batch;
   a.x0 = x0;
   a.xref = x_ref;

@@ -42,6 +42,7 @@
 #include <type_traits>
 
 #include "qloco_srbd_core.hpp"
+#include "qloco_srbd_model.hpp"
 
 namespace qloco {
 
@@ -437,34 +438,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
     }
   }
   float Ii[3][3];
-  {
-    const float *I = a.inertia;
-    const float Rm[3][3] = {{R00, R01, 0.f}, {R10, R11, 0.f}, {0.f, 0.f, 1.f}};
-    float RI[3][3], Iw[3][3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        RI[r][c] = Rm[r][0] * I[c * 3 + 0] + Rm[r][1] * I[c * 3 + 1] + Rm[r][2] * I[c * 3 + 2];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-      for (int c = 0; c < 3; ++c)
-        Iw[r][c] = RI[r][0] * Rm[c][0] + RI[r][1] * Rm[c][1] + RI[r][2] * Rm[c][2];
-    const float c00 = Iw[1][1] * Iw[2][2] - Iw[1][2] * Iw[2][1];
-    const float c01 = Iw[1][2] * Iw[2][0] - Iw[1][0] * Iw[2][2];
-    const float c02 = Iw[1][0] * Iw[2][1] - Iw[1][1] * Iw[2][0];
-    const float id = 1.0f / (Iw[0][0] * c00 + Iw[0][1] * c01 + Iw[0][2] * c02);
-    Ii[0][0] = c00 * id;
-    Ii[1][0] = c01 * id;
-    Ii[2][0] = c02 * id;
-    Ii[0][1] = (Iw[0][2] * Iw[2][1] - Iw[0][1] * Iw[2][2]) * id;
-    Ii[1][1] = (Iw[0][0] * Iw[2][2] - Iw[0][2] * Iw[2][0]) * id;
-    Ii[2][1] = (Iw[0][1] * Iw[2][0] - Iw[0][0] * Iw[2][1]) * id;
-    Ii[0][2] = (Iw[0][1] * Iw[1][2] - Iw[0][2] * Iw[1][1]) * id;
-    Ii[1][2] = (Iw[0][2] * Iw[1][0] - Iw[0][0] * Iw[1][2]) * id;
-    Ii[2][2] = (Iw[0][0] * Iw[1][1] - Iw[0][1] * Iw[1][0]) * id;
-  }
+  srbd_inertia_inv(cy, sy, a.inertia, Ii);
   // per slot: the variable, its B_d column (omega rows: ba) and E column
   const int comp = lane % 3;
   const bool xy = comp < 2;
@@ -478,20 +452,9 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
     step[h] = valid[h] ? so + v / 12 : 0;
     cst[h] = W == 1 ? step[h] : (valid[h] ? 10 * wv + v / 12 : 0);
     leg[h] = valid[h] ? (v % 12) / 3 : 0;
-    const float *rf = a.feet + b * 12 + 3 * leg[h];
-    const float rx = rf[0], ry = rf[1], rz = rf[2];
-    const float tv0 = comp == 0 ? 0.f : (comp == 1 ? -rz : ry);  // skew(r) e_comp (Utils.cpp:35-41)
-    const float tv1 = comp == 0 ? rz : (comp == 1 ? 0.f : -rx);
-    const float tv2 = comp == 0 ? -ry : (comp == 1 ? rx : 0.f);
-    float ba[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) ba[r] = dt * (Ii[r][0] * tv0 + Ii[r][1] * tv1 + Ii[r][2] * tv2);
-    lo[h] = (f4v){ba[0], ba[1], ba[2], dt * (R00 * ba[0] + R01 * ba[1])};
-    hi[h] = (f4v){dt * (R10 * ba[0] + R11 * ba[1]), dt * ba[2], (float)step[h], (float)comp};
-    if (!valid[h]) {
-      lo[h] = (f4v)(0.0f);
-      hi[h] = (f4v){0.0f, 0.0f, 0.0f, -1.0f};
-    }
+    float ba[3];  // constant feet only (srbd_route_of)
+    srbd_bd_column(Ii, srbd_foot(a.feet, b, N, 0, step[h], leg[h]), comp, dt, R00, R01, R10, R11,
+                   step[h], valid[h], ba, lo[h], hi[h]);
     // the wrench map (constant feet): column v % 12 of Bb from the step-0 lanes
     if (h == 0 && tid < 12) {
       S.Bb[0][lane] = ba[0];
@@ -520,20 +483,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
   // ---------------- 3. gradient g = Bqp' Q (Aqp x0 - x_ref) (ConvexMpc.cpp:219-221)
   for (int idx = tid; idx < 12 * N; idx += 64 * W) {
     const int i = idx / 12, s = idx - 12 * i;
-    const float k = (float)(i + 1);
-    const float *x0 = S.x0;
-    float xf;
-    if (s < 3) {
-      const float rw = s == 0 ? (R00 * x0[6] + R01 * x0[7]) : (s == 1 ? (R10 * x0[6] + R11 * x0[7]) : x0[8]);
-      xf = x0[s] + k * dt * rw;
-    } else if (s < 6) {
-      xf = x0[s] + k * dt * x0[s + 6];
-      if (s == 5) xf += 0.5f * k * (k - 1.0f) * dt * dt * x0[12];
-    } else if (s < 9) {
-      xf = x0[s];
-    } else {
-      xf = x0[s] + (s == 11 ? k * dt * x0[12] : 0.0f);
-    }
+    const float xf = srbd_free_state<12>(S.x0, s, i, dt, R00, R01, R10, R11);
     S.err[idx] = S.q2[s] * (xf - a.xref[b * 13 * N + 13 * i + s]);
   }
   bsync<W>();

@@ -24,19 +24,16 @@
 #include <mutex>
 
 #include "qloco.h"
+#include "qloco_srbd_spec.hpp"
 #include "qloco_srbd_tables.hpp"
 
 namespace qloco {
 
-namespace {
-constexpr int kOneWaveN = 10, kTwoWaveN = 20;  // kLitN / kLitN2 (qloco_srbd_core.hpp)
-}
-
 bool srbd_lit_tables_host(int N, float dt, const float *q2, float *gtab, float *sq, float *gmx) {
-  if (N < 1 || N > kTwoWaveN) return false;
+  if (N < 1 || N > kLitN2) return false;
   if (!(q2[6] > 0.0f) || q2[6] != q2[7]) return false;
-  const int NT = N <= kOneWaveN ? kOneWaveN : kTwoWaveN;
-  const int H = N <= kOneWaveN ? N : (N + 1) / 2;
+  const int NT = N <= kLitN ? kLitN : kLitN2;
+  const int H = N <= kLitN ? N : (N + 1) / 2;
   const double dt2 = (double)dt * (double)dt;
   const double ix = 1.0 / sqrt((double)q2[6]);
   const double lam[2] = {(double)q2[0] * ix * ix, (double)q2[1] * ix * ix};
@@ -46,7 +43,7 @@ bool srbd_lit_tables_host(int N, float dt, const float *q2, float *gtab, float *
     const double al = ax < 2 ? 1.0 : (ax == 2 ? (double)q2[8] : (double)q2[9 + ax - 3]);
     const double be = ax < 2 ? dt2 * lam[ax] : dt2 * (double)q2[ax];  // q_theta_z / q_p: q2[2..5]
     const double sn2 = ax < 2 ? ix * ix : 1.0;  // |S column|^2 (the gmx bound)
-    double A[kTwoWaveN][kTwoWaveN];
+    double A[kLitN2][kLitN2];
     for (int ri = 0; ri < N; ++ri)
       for (int k = 0; k < N; ++k) {
         const int M = ri > k ? ri : k;
@@ -58,7 +55,7 @@ bool srbd_lit_tables_host(int N, float dt, const float *q2, float *gtab, float *
     // in-place Gauss-Jordan, every row against the pivot row as it stood
     // before the pivot (the kernel's lanes read it from an LDS copy)
     for (int k = 0; k < N; ++k) {
-      double pr[kTwoWaveN];
+      double pr[kLitN2];
       for (int c = 0; c < N; ++c) pr[c] = A[k][c];
       const double pinv = 1.0 / pr[k];
       for (int ri = 0; ri < N; ++ri) {
@@ -72,9 +69,9 @@ bool srbd_lit_tables_host(int N, float dt, const float *q2, float *gtab, float *
       }
     }
     for (int ri = 0; ri < N; ++ri) {
-      const int csi = ri < H ? ri : kOneWaveN + ri - H;
+      const int csi = ri < H ? ri : kLitN + ri - H;
       for (int k = 0; k < N; ++k) {
-        const int csk = k < H ? k : kOneWaveN + k - H;
+        const int csk = k < H ? k : kLitN + k - H;
         gtab[(csi * NT + csk) * 6 + ax] = (float)A[ri][k];
       }
       dmax = fmaxf(dmax, (float)(sn2 * A[ri][ri]));
@@ -90,7 +87,7 @@ struct TabEntry {
   bool used = false;
   int N = 0;
   float dt = 0.0f, q2[12] = {}, sq = 0.0f, gmx = 0.0f;
-  float gtab[kOneWaveN * kOneWaveN * 6] = {};
+  float gtab[kLitN * kLitN * 6] = {};
 };
 constexpr int kTabEntries = 8;
 std::mutex g_tab_mu;
@@ -99,7 +96,7 @@ int g_tab_next = 0;
 }  // namespace
 
 bool srbd_lit_tables_cached(int N, float dt, const float *q2, float *gtab, float *sq, float *gmx) {
-  if (N < 1 || N > kOneWaveN) return false;
+  if (N < 1 || N > kLitN) return false;
   if (!(q2[6] > 0.0f) || q2[6] != q2[7]) return false;
   std::lock_guard<std::mutex> lk(g_tab_mu);
   TabEntry *e = nullptr;
@@ -129,11 +126,11 @@ extern "C" int qloco_srbd_lit_tables(const qloco_srbd_spec *spec, float *gtab, i
                                      float *s_scale, float *gmx, int32_t *served) {
   if (!spec || !gtab || !s_scale || !gmx || !served) return QLOCO_ERR_ARG;
   const int N = spec->horizon;
-  if (N < 1 || N > qloco::kTwoWaveN) return QLOCO_BAD_SIZE;
-  const int NT = N <= qloco::kOneWaveN ? qloco::kOneWaveN : qloco::kTwoWaveN;
+  if (N < 1 || N > qloco::kLitN2) return QLOCO_BAD_SIZE;
+  const int NT = N <= qloco::kLitN ? qloco::kLitN : qloco::kLitN2;
   if (gtab_len < (int64_t)NT * NT * 6) return QLOCO_ERR_ARG;
   float q2[13];
-  for (int k = 0; k < 13; ++k) q2[k] = 2.0f * spec->q_weights[k];
+  qloco::srbd_doubled_weights(spec, q2, nullptr);
   *served = qloco::srbd_lit_tables_host(N, spec->dt, q2, gtab, s_scale, gmx) ? 1 : 0;
   return QLOCO_OK;
 }

@@ -693,6 +693,65 @@ def test_srbd_wide_warm_and_persistent():
     assert same >= 0.7 * total, (same, total)
 
 
+@pytest.mark.parametrize("N,B,gait,lit,legs", [(3, 8, "trot", 0, 6), (11, 4, "trot", 0, 22),
+                                               (11, 2, "stance", 0, 44), (3, 4, "trot", 1, 6)])
+def test_srbd_per_step_feet_reach_every_solve_kernel(N, B, gait, lit, legs):
+    """feet_per_step = 1 (feet of shape (B, 12 N): the generated feet tiled
+    over the horizon plus a seeded uniform jitter of +-0.02 m, as in
+    test_srbd_dense_build_matches_restatement) through each solve kernel
+    family at its smallest shape: 6 stance legs -> the one-wave short-horizon
+    kernel, 22 -> the two-wave bucket C2 = 3, 44 -> the wide kernel at
+    HC = 96, and the literal full QP, which per-step feet route to the
+    generic literal kernels (QLOCO_ROUTE_LIT_GENERIC).  Per instance against
+    Instance(..., feet_per_step=1): status OK; iterations within two check
+    intervals of admm_reduced() (admm_full() for the literal QP); the
+    objective criteria of test_srbd_wide_instances_match_restatement
+    (objective gap to the exact optimum within 1e-3 of the restatement's own,
+    reported obj within 1e-3 relative, u exactly 0 on swing legs -- on the
+    literal QP the swing forces are ADMM variables held by fz in [0, 0]
+    rows, zero within the literal tests' 0.25 N, not bit-exact).
+
+    The two restatement-only CPU checks behind the jitter amplitude (seed 9,
+    +-0.02 m, these four batches):
+      * the restatement solves all 8 + 4 + 2 + 4 jittered instances with
+        status OK (25 .. 200 iterations);
+      * its solution of the problem with step 0's feet held over the horizon
+        misses the objective-gap criterion on the jittered problem in 6 of 8,
+        4 of 4, 2 of 2 and 4 of 4 instances (gaps 1.1e-3 .. 1.1e-2, 3.7e-3 ..
+        0.27, 1.1e-2 .. 1.3e-2, 1.2e-3 .. 1.1e-2), so a kernel that read
+        constant feet would fail here."""
+    dev = _dev()
+    x0, xr, ft, ct = srbd.generate(SEED, N, B, gait)
+    rng = np.random.default_rng(9)
+    ft = (np.tile(ft, (1, N)) + rng.uniform(-0.02, 0.02, (B, 12 * N))).astype(np.float32)
+    assert (ct.reshape(B, -1).sum(1) == legs).all()
+    if lit:
+        assert srbd.route(srbd.default_spec(horizon=N, literal_full_qp=1, feet_per_step=1)) == 3
+    solver = srbd.BatchedConvexMpc(horizon=N, literal_full_qp=lit)
+    out = solver.solve(*(torch.from_numpy(a).to(dev) for a in (x0, xr, ft, ct)), full=True)
+    torch.cuda.synchronize()
+    assert solver.spec.feet_per_step == 1
+    r = {k: getattr(out, k).cpu().numpy() for k in ("u0", "u", "status", "iters", "obj")}
+    sp = O.srbd_spec(N=N)
+    for b in range(B):
+        inst = Instance(sp, x0[b], xr[b], ft[b], ct[b], feet_per_step=1)
+        xa, info = inst.admm_full() if lit else inst.admm_reduced()
+        u = r["u"][b].astype(np.float64)
+        fe = inst.exact_obj()
+        sc = max(1.0, abs(fe))
+        gap = abs((inst.obj(u) - fe) / sc - (inst.obj(xa) - fe) / sc)
+        swing = np.abs(u[np.repeat(ct[b] == 0, 3)]).max(initial=0.0)  # all-stance: no swing leg
+        print("per-step feet N=%d %s lit=%d b=%d: status %d iters %d (restatement %d) gap %.3e obj %.6g / %.6g "
+              "swing max %.3e" % (N, gait, lit, b, r["status"][b], r["iters"][b], info.iters, gap,
+                                   r["obj"][b], inst.obj(u), swing))
+        assert r["status"][b] == 0 and info.status == 0, (b, r["status"][b], info.status)
+        assert abs(int(r["iters"][b]) - info.iters) <= 50, (b, r["iters"][b], info.iters)
+        assert gap <= 1e-3, (b, gap)
+        assert abs(r["obj"][b] - inst.obj(u)) <= 1e-3 * max(1.0, abs(inst.obj(u))), (b, r["obj"][b])
+        assert swing == 0.0 if not lit else swing <= 0.25, (b, swing)
+        assert np.array_equal(r["u0"][b], r["u"][b][:12])
+
+
 # --- the literal full QP (spec.literal_full_qp = 1): the reference's call as
 # written -- all 12N forces are ADMM variables, swing legs held by their
 # fz in [0, 0] rows (OSQP equality rows, rho_eq = 1e3 rho), Ruiz over the

@@ -1,5 +1,8 @@
 """Run one SRBD kernel configuration repeatedly (for rocprofv3 counter passes
-and batch-size scans).  Usage: python tools/perf_kernel.py VARIANT [B] [REPS]"""
+and batch-size scans).  Usage: python tools/perf_kernel.py VARIANT [B] [REPS]
+Environment: N, GAIT, LITERAL=1 (the literal QP), WARM=1 / 2 (warm start /
+persistent record: the warm-start kernel instantiations, resumed every call),
+BUILD=1 (the dense build, qloco_srbd_build, instead of a solve)."""
 import os
 import sys
 
@@ -37,20 +40,29 @@ legs = srbd.max_stance_legs(ct, N)
 LIT = int(os.environ.get("LITERAL", 0))  # 1: the literal 12N-variable QP
 if LIT:
     legs = 4 * N
-s = srbd.BatchedConvexMpc(horizon=N, literal_full_qp=LIT, **VARIANTS[name])
+WARM = int(os.environ.get("WARM", 0))
+s = srbd.BatchedConvexMpc(horizon=N, literal_full_qp=LIT, warm_start=WARM, **VARIANTS[name])
 out = s.alloc_outputs(B, dev)
+warm = torch.zeros((B, srbd.persist_len(N) if WARM == 2 else 32 * N), dtype=torch.float32, device=dev) if WARM else None
+if int(os.environ.get("BUILD", 0)):
+    name = "build"
+    out.iters.zero_()
+    out.rho_updates.zero_()
+    run = lambda: s.build(*args)
+else:
+    run = lambda: s.solve(*args, out=out, max_legs=legs, warm=warm)
 for _ in range(2):
-    s.solve(*args, out=out, max_legs=legs)
+    run()
 torch.cuda.synchronize()
 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
 e0.record()
 for _ in range(reps):
-    s.solve(*args, out=out, max_legs=legs)
+    run()
 e1.record()
 torch.cuda.synchronize()
 it = out.iters.float()
 print("%-10s %-6s%s N=%-2d %-8s B=%6d  %9.1f us/launch  iters mean %.1f p99 %d max %d  rho_updates mean %.2f max %d" % (
     os.path.basename(os.path.dirname(os.environ.get("QLOCO_LIB", "/prod/x"))), GAIT,
-    " lit" if LIT else "", N, name, B,
+    (" lit" if LIT else "") + (" warm%d" % WARM if WARM else ""), N, name, B,
     e0.elapsed_time(e1) / reps * 1e3, it.mean().item(), int(it.quantile(0.99).item()), int(it.max().item()),
     out.rho_updates.float().mean().item(), int(out.rho_updates.max().item())), flush=True)
