@@ -96,7 +96,10 @@ typedef struct qloco_srbd_spec {
   int32_t reserved[5];       /* zero, but for the debug bit reserved[0] & 1: the one-  */
                              /* wave literal kernel builds its G^-1 horizon tables  */
                              /* per instance although the spec has host tables       */
-                             /* (qloco_srbd_lit_tables); both paths stay tested      */
+                             /* (qloco_srbd_lit_tables); both paths stay tested;     */
+                             /* and reserved[1] > 0: the SIMD count the placement    */
+                             /* state assumes instead of the device's (tests reach   */
+                             /* qloco_srbd_solve_placed's path at small batches)     */
 } qloco_srbd_spec;
 
 /* Per-instance record of the persistent solver (spec.warm_start == 2),
@@ -167,6 +170,40 @@ int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, const float 
                         float *u0, float *u, int32_t *status, int32_t *iters,
                         int32_t *rho_updates, float *obj, float *warm,
                         int32_t max_stance_legs, void *stream);
+
+/* qloco_srbd_solve_ex with a placement state: `place`, device memory of
+ * qloco_srbd_place_bytes(batch) bytes that the caller owns, zeroes once and
+ * passes to every call of one controller batch (NULL = qloco_srbd_solve_ex).
+ * A cold one-wave literal launch ends with its most loaded SIMD (DESIGN.md
+ * §3q), so each call leaves every instance's iteration count in the state
+ * and a small kernel after the solve, on the same stream, orders the next
+ * call: the longest instances one per SIMD, each with the shortest ones left
+ * as companions.  Only which workgroup solves an instance changes: every
+ * output array is byte-identical to a call without the state, whatever the
+ * state holds, and a controller whose counts drift or jump only loses the
+ * gain.  The state is int32 words: a 4-word header (word 0 = batch once the
+ * order is valid), hint[batch], order[batch]; all zero = no order yet.
+ * It is used where QLOCO_ROUTE_LIT_ONE_WAVE runs with warm_start = 0 and
+ * S < batch <= 4 S, S = 4 x the device's compute units (the batch resident at
+ * once, more than one wave per SIMD); every other call ignores the pointer.
+ * One stream at a time per state, as for the persistent record: calls that
+ * share a state must be ordered on the device.  Write nothing into a state
+ * but zeros. */
+int64_t qloco_srbd_place_bytes(int64_t batch);
+int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                            const float *x_ref, const float *feet, const uint8_t *contacts,
+                            float *u0, float *u, int32_t *status, int32_t *iters,
+                            int32_t *rho_updates, float *obj, float *warm,
+                            int32_t max_stance_legs, int32_t *place, void *stream);
+
+/* The ordering kernel's arithmetic on the host (tests): order[batch] from
+ * hint[batch] for `simds` SIMDs, simds < batch <= 4 simds.  Instances by class
+ * min(hint / max(check_termination, 1), 255), clamped at 0, the highest class
+ * first; position s + simds q holds rank s for q = 0 and, from the short end,
+ * SIMD s's q-th companion otherwise.  Any hint[] gives a permutation.  Host
+ * pointers; QLOCO_ERR_ARG outside that range. */
+int qloco_srbd_place_order_host(int64_t batch, int64_t simds, int32_t check_termination,
+                                const int32_t *hint, int32_t *order);
 
 /* The kernel family a qloco_srbd_solve[_ex] call with this spec runs
  * (host-only, no device work; the solve uses the same decision):

@@ -22,6 +22,7 @@ SOURCES = [
     "qloco_capi.hip",
     "qloco_srbd.hip",
     "qloco_srbd_lit.hip",
+    "qloco_srbd_place.hip",
     "qloco_srbd_build.hip",
     "qloco_kin.hip",
     "qloco_gi.hip",

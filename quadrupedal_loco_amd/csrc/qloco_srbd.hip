@@ -1424,12 +1424,12 @@ extern "C" int qloco_srbd_route(const qloco_srbd_spec *spec) {
   return srbd_route_of(a);
 }
 
-extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
-                                   const float *x_ref, const float *feet,
-                                   const uint8_t *contacts, float *u0, float *u,
-                                   int32_t *status, int32_t *iters, int32_t *rho_updates,
-                                   float *obj, float *warm, int32_t max_stance_legs,
-                                   void *stream) {
+extern "C" int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                       const float *x_ref, const float *feet,
+                                       const uint8_t *contacts, float *u0, float *u,
+                                       int32_t *status, int32_t *iters, int32_t *rho_updates,
+                                       float *obj, float *warm, int32_t max_stance_legs,
+                                       int32_t *place, void *stream) {
   if (!spec || batch < 0) return QLOCO_ERR_ARG;
   if (spec->horizon < 1 || spec->horizon > kMaxN) return QLOCO_BAD_SIZE;
   if (batch == 0) return QLOCO_OK;
@@ -1526,7 +1526,11 @@ extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, c
     // kernel arguments; reserved[0] & 1 keeps the in-kernel path
     if (a.N <= kLitN && !(spec->reserved[0] & 1))
       a.lit_tables = srbd_lit_tables_cached(a.N, a.dt, a.q2, a.lit_gtab, &a.lit_sq, &a.lit_gmx) ? 1 : 0;
-    const int rc = srbd_lit_launch(a, ws, st);
+    // the placement state serves the one-wave kernel's cold solves alone;
+    // reserved[1]: the SIMD count it assumes (tests; 0 = the device's)
+    const bool one_wave = a.N <= kLitN;
+    const int rc = srbd_lit_launch(a, ws, one_wave ? place : nullptr,
+                                   spec->reserved[1] > 0 ? spec->reserved[1] : 0, st);
     if (rc != QLOCO_OK) return rc;
   } else if (top == 0 || a.literal) {
     // one class: every instance of the literal QP has 4N leg triples, so no
@@ -1595,6 +1599,16 @@ extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, c
   }
   QLOCO_HIP_CHECK(hipGetLastError(), "srbd_admm_kernel launch");
   return QLOCO_OK;
+}
+
+extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                   const float *x_ref, const float *feet,
+                                   const uint8_t *contacts, float *u0, float *u,
+                                   int32_t *status, int32_t *iters, int32_t *rho_updates,
+                                   float *obj, float *warm, int32_t max_stance_legs,
+                                   void *stream) {
+  return qloco_srbd_solve_placed(spec, batch, x0, x_ref, feet, contacts, u0, u, status, iters,
+                                 rho_updates, obj, warm, max_stance_legs, nullptr, stream);
 }
 
 extern "C" int qloco_srbd_solve(const qloco_srbd_spec *spec, int64_t batch, const float *x0,

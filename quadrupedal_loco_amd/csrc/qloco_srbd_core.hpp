@@ -2,6 +2,7 @@
 // units (qloco_srbd.hip: the stance-only and two-wave / wide classes;
 // qloco_srbd_lit.hip: the literal QP through the wrench space).
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <type_traits>
@@ -38,6 +39,12 @@ struct SrbdArgs {
   // device-side length (qloco_srbd_solve_ex's class lists)
   const int *list;
   const int *count;
+  // one-wave literal kernel, cold start: the caller's placement state
+  // (qloco_srbd_place.hpp).  hint[b] takes instance b's iteration count;
+  // workgroup p solves instance order[p] once the state's ready word, at
+  // hint[-kPlaceHeader], equals the batch.  NULL: workgroup p solves p.
+  int *hint;
+  const int *order;
   // one-wave literal kernel: the G^-1 horizon tables of the spec, computed on
   // the host once per spec (qloco_srbd_tables.cpp) and carried in the kernel
   // arguments -- no launch, no allocation, no copy of their own, and a
@@ -223,6 +230,13 @@ __device__ __forceinline__ void k0k2(float ja, float jb, float Nf, float &K0, fl
 // Gauss-Jordan: pivots above this get their column written exactly (qloco_srbd.hip)
 constexpr float kGjExactPivot = 16.0f;
 
-int srbd_lit_launch(const SrbdArgs &a, bool warm, hipStream_t stream);
+static_assert(sizeof(SrbdArgs) <= 4096, "kernel argument segment");
+static_assert(offsetof(SrbdArgs, lit_gtab) % 16 == 0, "lit_gtab is read in 16-byte chunks");
+
+// place: the caller's placement state or NULL; simds: spec.reserved[1]
+// (0 = four per compute unit of the current device)
+int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hipStream_t stream);
+int srbd_place_launch(int32_t *place, int64_t batch, int simds, int check_termination,
+                      hipStream_t stream);
 
 }  // namespace qloco

@@ -43,6 +43,7 @@
 
 #include "qloco_srbd_core.hpp"
 #include "qloco_srbd_model.hpp"
+#include "qloco_srbd_place.hpp"
 
 namespace qloco {
 
@@ -1623,6 +1624,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
   if (tid_o == 0) {
     if (a.status) a.status[b] = status;
     if (a.iters) a.iters[b] = S.sc[wv].iter;
+    if (a.hint) a.hint[b] = S.sc[wv].iter;  // placement state: the next call's order
     if (a.rho_updates) a.rho_updates[b] = S.sc[wv].rho_updates;
     if (a.obj) a.obj[b] = objp;
   }
@@ -1632,8 +1634,12 @@ template <bool WS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLitWpe)))
 void srbd_lit_kernel(const SrbdArgs a) {
   __shared__ __attribute__((aligned(16))) LitLds<1> S;
-  const int64_t i = blockIdx.x;
-  if (i >= a.batch) return;
+  // the placement state's order (qloco_srbd_place.hpp) once it is ready for
+  // this batch: which workgroup solves an instance, never what it computes
+  // or where its outputs go (uniform loads)
+  int64_t i = blockIdx.x;
+  if (a.order && a.hint[-kPlaceHeader] == a.batch) i = a.order[blockIdx.x];
+  if (i < 0 || i >= a.batch) return;
   srbd_lit_one<1, WS>(a, S, i);
 }
 
@@ -1646,14 +1652,50 @@ void srbd_lit2_kernel(const SrbdArgs a) {
   srbd_lit_one<2, WS>(a, S, i);
 }
 
-int srbd_lit_launch(const SrbdArgs &a, bool warm, hipStream_t stream) {
+// SIMDs of the current device (four per compute unit), asked once per device
+static int device_simds(int *simds) {
+  constexpr int kDevs = 64;
+  static int cached[kDevs];
+  int dev = 0, cus = 0;
+  QLOCO_HIP_CHECK(hipGetDevice(&dev), "hipGetDevice");
+  if (dev >= 0 && dev < kDevs && cached[dev] > 0) {
+    *simds = cached[dev];
+    return QLOCO_OK;
+  }
+  QLOCO_HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev),
+                  "hipDeviceGetAttribute");
+  *simds = 4 * cus;
+  if (dev >= 0 && dev < kDevs) cached[dev] = *simds;
+  return QLOCO_OK;
+}
+
+int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hipStream_t stream) {
   const dim3 grid((unsigned)a.batch);
   if (a.N < 1 || a.N > kLitN2) return QLOCO_BAD_SIZE;
   if (a.N <= kLitN) {
-    if (warm)
+    if (warm) {
       hipLaunchKernelGGL(srbd_lit_kernel<true>, grid, dim3(64), 0, stream, a);
-    else
-      hipLaunchKernelGGL(srbd_lit_kernel<false>, grid, dim3(64), 0, stream, a);
+    } else {
+      // cold solves of a batch that is resident at once but fills more than
+      // one wave slot per SIMD: the launch ends with its most loaded SIMD, so
+      // the instances are placed by their last iteration counts
+      SrbdArgs ap = a;
+      bool placed = false;
+      if (place) {
+        if (simds <= 0) {
+          const int rc = device_simds(&simds);
+          if (rc != QLOCO_OK) return rc;
+        }
+        placed = a.batch > simds && a.batch <= (int64_t)kLitWpe * simds;
+      }
+      if (placed) {
+        ap.hint = place + kPlaceHeader;
+        ap.order = place + kPlaceHeader + a.batch;
+      }
+      hipLaunchKernelGGL(srbd_lit_kernel<false>, grid, dim3(64), 0, stream, ap);
+      QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit_kernel launch");
+      if (placed) return srbd_place_launch(place, a.batch, simds, a.check_termination, stream);
+    }
     QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit_kernel launch");
   } else {
     if (warm)

@@ -21,6 +21,7 @@ import numpy as np
 from ._lib import SrbdSpec, check, lib, ptr
 
 GAITS = {"trot": 0, "pace": 1, "biped": 1, "mixed": 2, "stance": 3}
+PLACE_STATES = 8  # placement states a BatchedConvexMpc keeps (one per batch, device, stream)
 
 # The MPC weight sets the reference ships, loaded by a1_ctrl.launch by `type`
 # (unitree_ros/a1_cpp_open_source/config/{gazebo,hardware,isaac}_a1_mpc.yaml,
@@ -193,12 +194,39 @@ class BatchedConvexMpc:
     reduction (same optimum, fewer variables).
     """
 
-    def __init__(self, spec=None, **overrides):
+    def __init__(self, spec=None, placement=True, **overrides):
         self.spec = spec if spec is not None else default_spec(**overrides)
+        self.placement = bool(placement)
+        self._place = {}  # (batch, device, stream) -> placement state, least recently used first
 
     @property
     def horizon(self):
         return self.spec.horizon
+
+    def place_state(self, batch, device, stream):
+        """The zero-initialised placement state (qloco_srbd_solve_placed) of
+        this solver's cold literal solves of `batch` instances on (device,
+        stream): int32 words, header | hint[batch] | order[batch].  One per
+        key, at most PLACE_STATES live (the least recently used one is dropped
+        after a device synchronisation).  None where one would have to be
+        allocated during a stream capture: that call runs unplaced."""
+        import torch
+        dev = torch.device(device)
+        key = (int(batch), dev.index if dev.index is not None else torch.cuda.current_device(),
+               int(stream))
+        st = self._place.pop(key, None)
+        if st is None:
+            if torch.cuda.is_current_stream_capturing():
+                return None
+            if len(self._place) >= PLACE_STATES:
+                torch.cuda.synchronize(dev)  # its last launch may still be running
+                self._place.pop(next(iter(self._place)))
+            words = lib().qloco_srbd_place_bytes(int(batch)) // 4
+            st = torch.zeros(words, dtype=torch.int32, device=dev)
+            # the fill runs on torch's current stream, the solve on `stream`
+            torch.cuda.current_stream(dev).synchronize()
+        self._place[key] = st
+        return st
 
     def alloc_outputs(self, batch, device, full=False, stats=True):
         import torch
@@ -229,10 +257,15 @@ class BatchedConvexMpc:
             out = self.alloc_outputs(B, x0.device, full=full)
         if stream is None:
             stream = torch.cuda.current_stream(x0.device).cuda_stream
-        check(lib().qloco_srbd_solve_ex(
+        # cold literal solves: instances placed on SIMDs by their last call's
+        # iteration counts (the library ignores the state on every other path)
+        place = None
+        if self.placement and self.spec.literal_full_qp and not self.spec.warm_start and B > 0:
+            place = self.place_state(B, x0.device, stream)
+        check(lib().qloco_srbd_solve_placed(
             C.byref(self.spec), B, ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts), ptr(out.u0),
             ptr(out.u), ptr(out.status), ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
-            ptr(warm), int(max_legs), C.c_void_p(stream)), "qloco_srbd_solve")
+            ptr(warm), int(max_legs), ptr(place), C.c_void_p(stream)), "qloco_srbd_solve")
         return out
 
     def build(self, x0, x_ref, feet, contacts=None, want=("H", "g", "lb", "ub"), stream=None):
@@ -281,7 +314,7 @@ class PersistentConvexMpc(BatchedConvexMpc):
 
     def __init__(self, batch, device, spec=None, **overrides):
         import torch
-        super().__init__(spec, **overrides)
+        super().__init__(spec, placement=False, **overrides)  # warm ticks have no tail to balance
         self.spec.warm_start = 2
         self.batch = int(batch)
         self.record = torch.zeros((self.batch, persist_len(self.spec.horizon)),
