@@ -177,8 +177,10 @@ int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, const float 
  * A cold one-wave literal launch ends with its most loaded SIMD (DESIGN.md
  * §3q), so each call leaves every instance's iteration count in the state
  * and a small kernel after the solve, on the same stream, orders the next
- * call: the longest instances one per SIMD, each with the shortest ones left
- * as companions.  Only which workgroup solves an instance changes: every
+ * call: the longest instances one per SIMD, the others dealt to them as
+ * companions by rank: short ones to the long heads, one long,
+ * one middle and one short to the rest.  Only which workgroup solves an
+ * instance changes: every
  * output array is byte-identical to a call without the state, whatever the
  * state holds, and a controller whose counts drift or jump only loses the
  * gain.  The state is int32 words: a 4-word header (word 0 = batch once the
@@ -204,6 +206,13 @@ int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const fl
  * pointers; QLOCO_ERR_ARG outside that range. */
 int qloco_srbd_place_order_host(int64_t batch, int64_t simds, int32_t check_termination,
                                 const int32_t *hint, int32_t *order);
+
+/* The solve kernel's choice of rank on the host (tests, tools):
+ * rank_of_position[p], p = s + simds q, is the rank (0 = longest) of the
+ * instance that workgroup p solves, taken from order[] at that rank's
+ * position.  A permutation of [0, batch) with rank s at q = 0.  Host pointer;
+ * the refusals of qloco_srbd_place_order_host. */
+int qloco_srbd_place_assign_host(int64_t batch, int64_t simds, int32_t *rank_of_position);
 
 /* The kernel family a qloco_srbd_solve[_ex] call with this spec runs
  * (host-only, no device work; the solve uses the same decision):

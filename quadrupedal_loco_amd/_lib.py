@@ -146,6 +146,7 @@ SIGNATURES = {
                                           vp, vp, vp, i32, vp, vp]),
     "qloco_srbd_place_bytes": (i64, [i64]),
     "qloco_srbd_place_order_host": (C.c_int, [i64, i64, i32, vp, vp]),
+    "qloco_srbd_place_assign_host": (C.c_int, [i64, i64, vp]),
     "qloco_srbd_build": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                    vp, vp, vp]),
     "qloco_gen_srbd_host": (C.c_int, [C.c_uint64, i32, C.c_float, i32, i64, i64, vp, vp, vp,

@@ -41,10 +41,13 @@ struct SrbdArgs {
   const int *count;
   // one-wave literal kernel, cold start: the caller's placement state
   // (qloco_srbd_place.hpp).  hint[b] takes instance b's iteration count;
-  // workgroup p solves instance order[p] once the state's ready word, at
+  // workgroup p solves the instance of rank place_assign(p), at
+  // order[place_position(rank)], once the state's ready word, at
   // hint[-kPlaceHeader], equals the batch.  NULL: workgroup p solves p.
+  // place_simds: the SIMD count S of both maps, S < batch <= 4 S.
   int *hint;
   const int *order;
+  int place_simds;
   // one-wave literal kernel: the G^-1 horizon tables of the spec, computed on
   // the host once per spec (qloco_srbd_tables.cpp) and carried in the kernel
   // arguments -- no launch, no allocation, no copy of their own, and a

@@ -1636,9 +1636,14 @@ void srbd_lit_kernel(const SrbdArgs a) {
   __shared__ __attribute__((aligned(16))) LitLds<1> S;
   // the placement state's order (qloco_srbd_place.hpp) once it is ready for
   // this batch: which workgroup solves an instance, never what it computes
-  // or where its outputs go (uniform loads)
+  // or where its outputs go.  The workgroup's rank is place_assign's (DESIGN.md
+  // §3r): uniform scalar arithmetic and two uniform loads
   int64_t i = blockIdx.x;
-  if (a.order && a.hint[-kPlaceHeader] == a.batch) i = a.order[blockIdx.x];
+  if (a.order && a.hint[-kPlaceHeader] == a.batch) {
+    const int64_t at = place_position(place_assign(i, a.batch, a.place_simds), a.batch, a.place_simds);
+    if (at < 0 || at >= a.batch) return;
+    i = a.order[at];
+  }
   if (i < 0 || i >= a.batch) return;
   srbd_lit_one<1, WS>(a, S, i);
 }
@@ -1691,6 +1696,7 @@ int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hip
       if (placed) {
         ap.hint = place + kPlaceHeader;
         ap.order = place + kPlaceHeader + a.batch;
+        ap.place_simds = simds;
       }
       hipLaunchKernelGGL(srbd_lit_kernel<false>, grid, dim3(64), 0, stream, ap);
       QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit_kernel launch");

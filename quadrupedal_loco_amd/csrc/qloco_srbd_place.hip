@@ -78,3 +78,13 @@ extern "C" int qloco_srbd_place_order_host(int64_t batch, int64_t simds, int32_t
   }
   return QLOCO_OK;
 }
+
+extern "C" int qloco_srbd_place_assign_host(int64_t batch, int64_t simds,
+                                            int32_t *rank_of_position) {
+  using namespace qloco;
+  if (!rank_of_position || simds < 1 || batch <= simds || batch > 4 * simds ||
+      batch > (int64_t)1 << 30)
+    return QLOCO_ERR_ARG;
+  for (int64_t p = 0; p < batch; ++p) rank_of_position[p] = (int32_t)place_assign(p, batch, simds);
+  return QLOCO_OK;
+}

@@ -11,7 +11,10 @@
 //   [0]                     ready: == batch once order[] holds a permutation
 //   [1, kPlaceHeader)       zero
 //   hint[batch]             iteration count of each instance's last solve
-//   order[batch]            workgroup position -> instance
+//   order[batch]            the instance of rank k at order[place_position(k)]
+//
+// Which rank a workgroup takes is the solve kernel's choice (place_assign,
+// DESIGN.md §3r): it never reads hint[], which its own launch overwrites.
 #pragma once
 #include <stdint.h>
 
@@ -56,6 +59,49 @@ __host__ __device__ inline int64_t place_position(int64_t k, int64_t B, int64_t 
     c = jj - (s - r) * (m - 1);
   }
   return s + S * (c + 1);
+}
+
+// Rank that the workgroup at position p = s + S q solves:
+// the solve kernel reads order[place_position(place_assign(p))].  order[] and
+// place_rank keep their meaning; this map alone decides which ranks share a
+// SIMD.  Rank-only integer arithmetic, a bijection of [0, B) for S < B <= 4 S.
+//
+// q = 0: rank s, as before: the S longest one per SIMD, each SIMD's first
+// workgroup.  The companions, ranks S .. B - 1, with m = ceil((B - S) / S)
+// rows of them, the last one on the first r SIMDs only:
+//   m = 1, or s < A1 = S / 64   place_rank: the shortest left, next to each
+//                               other (a head far above the rest ends its
+//                               SIMD alone whatever joins it)
+//   A1 <= s < A2 = 3 S / 16     q = 1: one of the longest companions; the
+//                               other rows: the shortest left, next to each
+//                               other
+//   s >= A2                     one companion of each stratum: q = 1 of the
+//                               longest, row m of the shortest left, the rows
+//                               between of the strata between
+// In every row a longer head takes a shorter companion.  place_rank gave the
+// short heads, most of the SIMDs, companions of one class, their own.
+__host__ __device__ inline int64_t place_assign(int64_t p, int64_t B, int64_t S) {
+  const int64_t s = p % S, q = p / S;
+  if (q == 0) return s;
+  const int64_t T = B - S, m = (T + S - 1) / S, r = T - (m - 1) * S;
+  const int64_t A1 = m < 2 ? S : S / 64, A2 = A1 > 3 * S / 16 ? A1 : 3 * S / 16;
+  const int64_t n2 = A2 - A1, n3 = S - A2;
+  // companions of the SIMDs before s: m on the first r, m - 1 on the rest
+  const int64_t before = s * (m - 1) + (s < r ? s : r);
+  if (s < A1) return B - 1 - (before + (q - 1));
+  if (s < A2) {
+    // ranks [S, S + n3) are zone three's q = 1 row, [S + n3, S + n3 + n2) this zone's
+    if (q == 1) return S + n3 + (A2 - 1 - s);
+    return B - 1 - (before - (s - A1) + (q - 2));
+  }
+  const int64_t i = s - A2;
+  if (q == 1) return S + (n3 - 1 - i);
+  // from the short end: what zones one and two took, row m's stratum (on the
+  // SIMDs of this zone that have a row m), then rows m - 1 .. 2
+  const int64_t taken = A2 * (m - 1) + (A2 < r ? A2 : r) - n2;
+  if (q == m) return B - 1 - (taken + i);
+  const int64_t last = r - A2 < 0 ? 0 : (r - A2 > n3 ? n3 : r - A2);
+  return B - 1 - (taken + last + (m - 1 - q) * n3 + i);
 }
 
 }  // namespace qloco

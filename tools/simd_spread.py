@@ -1,11 +1,14 @@
 """Per-SIMD end-time spread of the literal N = 10 kernel at the headline batch
 (the tail the one-wave-per-instance launch waits on).
 
-    python tools/simd_spread.py build          (CPU: builds tools/_var/spread/libqloco.so)
+    python tools/simd_spread.py build [map]    (CPU: builds tools/_var/spread/libqloco.so)
     QLOCO_LIB=tools/_var/spread/libqloco.so python tools/simd_spread.py run [B] [GAIT] [shuffle] [noplace]   (GPU)
 
 noplace: the solver without its placement state, workgroup p
-solving instance p.
+solving instance p.  build map: tools/_var/spread_map/libqloco.so, workgroup p
+solving order[p] (the placement map alone, before place_assign, §3r).  With
+the state the run also prints how the SIMDs' four iteration counts compare
+with the assignment's on the same counts.
 
 The variant (tools/variant_lib.py --patch, never the product library) wraps
 srbd_lit_kernel: lane 0 of every workgroup reads the 100 MHz real-time
@@ -42,9 +45,17 @@ NEW = """  if (i < 0 || i >= a.batch) return;
 }"""
 
 
-def build():
+# the solve kernel's choice of rank (place_assign, DESIGN.md §3r) against the
+# placement map alone (workgroup p solves order[p], §3q)
+ASSIGN = "place_position(place_assign(i, a.batch, a.place_simds), a.batch, a.place_simds)"
+
+
+def build(old_assignment=False):
     import variant_lib
-    variant_lib.main(["spread", "--patch", "qloco_srbd_lit.hip:" + OLD + "=>" + NEW])
+    patches = ["--patch", "qloco_srbd_lit.hip:" + OLD + "=>" + NEW]
+    if old_assignment:
+        patches += ["--patch", "qloco_srbd_lit.hip:" + ASSIGN + "=>i"]
+    variant_lib.main(["spread_map" if old_assignment else "spread"] + patches)
 
 
 def run(B, gait, shuffle=False, placement=True):
@@ -107,6 +118,20 @@ def run(B, gait, shuffle=False, placement=True):
             same = np.mean([len(set((wg[inv == k] % nsimd).tolist())) == 1 for k in range(nsimd)])
             print("   placement: %.3f of SIMDs hold workgroups with one value of p mod %d; "
                   "SIMD key of workgroups 0..7: %s" % (same, nsimd, key[np.argsort(wg)[:8]].tolist()))
+            if placement and nsimd < B <= 4 * nsimd and hasattr(_lib.lib(), "qloco_srbd_place_assign_host"):
+                # the four counts of every SIMD against place_assign's on these counts
+                # (as multisets of sorted tuples: the order inside a class is the atomics')
+                import collections
+                import lit_placement_model as M
+                want = M._per_simd(it, M.assigned_order(it, nsimd), nsimd).astype(int)
+                got = np.zeros((nsimd, 4), int)
+                for k in range(nsimd):
+                    c = np.sort(it[inv == k])[-4:]
+                    got[k, 4 - len(c):] = c
+                cw = collections.Counter(map(tuple, want))
+                cg = collections.Counter(map(tuple, got))
+                print("   assignment: %d of %d SIMDs hold the counts place_assign gives; modelled span %.1f us" % (
+                    sum((cw & cg).values()), nsimd, M.simd_us(it, M.assigned_order(it, nsimd), nsimd).max()))
             late = np.argsort(-end)[:3]
             for k in late:
                 sel = inv == k
@@ -117,7 +142,7 @@ def run(B, gait, shuffle=False, placement=True):
 
 if __name__ == "__main__":
     if sys.argv[1] == "build":
-        build()
+        build("map" in sys.argv[2:])
     else:
         run(int(sys.argv[2]) if len(sys.argv) > 2 else 4096, sys.argv[3] if len(sys.argv) > 3 else "trot",
             "shuffle" in sys.argv[4:], "noplace" not in sys.argv[4:])
