@@ -43,7 +43,9 @@ typedef enum qloco_status {
   QLOCO_DEGENERATE = 6,        /* dependent equalities (EiQuadProg.cpp:270-275)       */
   QLOCO_UB_PATH = 7,           /* reference reads an uninitialised index (:105-110)   */
   QLOCO_SOLVED_INACCURATE = 8, /* OSQP_SOLVED_INACCURATE                              */
-  QLOCO_ERR_ARG = 100,         /* invalid argument (call-level)                       */
+  QLOCO_ERR_ARG = 100,         /* invalid argument (call-level); in a per-instance    */
+                               /* status array only from qloco_srbd_solve_model: that */
+                               /* instance's model row is invalid                     */
   QLOCO_ERR_DEVICE = 101,      /* HIP runtime error (call-level)                      */
   QLOCO_ERR_NO_GPU = 102       /* no gfx950 device visible                            */
 } qloco_status;
@@ -198,6 +200,57 @@ int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const fl
                             int32_t *rho_updates, float *obj, float *warm,
                             int32_t max_stance_legs, int32_t *place, void *stream);
 
+/* Per-instance body of the SRBD MPC: the five quantities of qloco_srbd_spec
+ * that describe the robot rather than the problem, one 64-byte row per
+ * instance.  A batch is a fleet: payload and friction randomised per robot,
+ * A1 and Go1 bodies mixed (a yaml per robot becomes a row per robot). */
+typedef struct qloco_srbd_model {
+  float mass;
+  float inertia[9];          /* col-major, as qloco_srbd_spec.inertia */
+  float mu, fz_min, fz_max;
+  float reserved[3];         /* zero */
+} qloco_srbd_model;
+
+/* rows[count] filled from the spec's mass, inertia, mu, fz_min and fz_max
+ * (reserved zero): start from the defaults, edit a few rows.  Host pointers,
+ * no device work. */
+int qloco_srbd_model_from_spec(const qloco_srbd_spec *spec, int64_t count, qloco_srbd_model *rows);
+
+/* qloco_srbd_solve_placed with per-instance bodies: `model` is device memory,
+ * batch rows, or NULL.  NULL is exactly qloco_srbd_solve_placed (which, like
+ * qloco_srbd_solve and _solve_ex, forwards here with NULL).  With rows,
+ * instance b takes mass, inertia, mu, fz_min and fz_max from model[b] and
+ * everything else from the spec; the spec's own five fields are then ignored,
+ * except that they are validated as before.  The rows are read during the
+ * call only and never written.
+ *   Kernels: every family a call can take honours the rows -- the one-wave
+ * literal kernel with and without the placement state (the row goes by the
+ * instance id, not by the workgroup that solves it), the two-wave literal
+ * kernel, the generic literal kernels, the reduced one- and two-wave classes
+ * and the wide kernel (the row goes by the instance id the class list holds,
+ * not by the position in the list).  The arithmetic is the uniform call's: an
+ * instance's outputs are byte-identical to those of a call without rows whose
+ * spec carries that row's values.  The route, the host G^-1 tables, the
+ * placement state and the persistent record's layout do not depend on the
+ * five quantities, and stay per batch; so do the weights and dt (they enter
+ * the tables and the route).
+ *   Warm start and the persistent solver: a controller's row may change
+ * between calls.  With literal_full_qp = 1 every call after the first already
+ * takes OSQP's update path with a new P, so nothing else happens.  With
+ * literal_full_qp = 0 the existing rule holds: the record re-initialises only
+ * when the stance set changes, a changed row alone takes the update path.
+ *   An invalid row -- one of its 13 values not finite, or mass <= 0 -- is not
+ * solved: that instance gets status QLOCO_ERR_ARG, NaN u0 / u / obj and
+ * iters = rho_updates = 0 (as QLOCO_BAD_SIZE does for its case), its warm /
+ * persistent record is left as it was, and every other instance of the batch
+ * is unaffected.  QLOCO_ERR_ARG is otherwise a call-level code. */
+int qloco_srbd_solve_model(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                           const float *x_ref, const float *feet, const uint8_t *contacts,
+                           float *u0, float *u, int32_t *status, int32_t *iters,
+                           int32_t *rho_updates, float *obj, float *warm,
+                           int32_t max_stance_legs, int32_t *place,
+                           const qloco_srbd_model *model, void *stream);
+
 /* The ordering kernel's arithmetic on the host (tests): order[batch] from
  * hint[batch] for `simds` SIMDs, simds < batch <= 4 simds.  Instances by class
  * min(hint / max(check_termination, 1), 255), clamped at 0, the highest class
@@ -250,6 +303,14 @@ int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, const float *x0
                      const float *x_ref, const float *feet, const uint8_t *contacts,
                      float *H, float *g, float *lb, float *ub, float *Aqp, float *Bqp,
                      void *stream);
+/* qloco_srbd_build with per-instance bodies (qloco_srbd_solve_model's rows:
+ * device memory, batch rows, or NULL = qloco_srbd_build).  mu enters none of
+ * these outputs.  The rows are not validated here: an invalid row gives what
+ * its arithmetic gives. */
+int qloco_srbd_build_model(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                           const float *x_ref, const float *feet, const uint8_t *contacts,
+                           float *H, float *g, float *lb, float *ub, float *Aqp, float *Bqp,
+                           const qloco_srbd_model *model, void *stream);
 
 /* Deterministic synthetic instances, host memory.
  * gait: 0 trot, 1 pace (reference gait_mode 101), 2 mixed per-step, 3 stance.
@@ -624,6 +685,13 @@ int qloco_mgpu_solve(qloco_mgpu *h, const qloco_srbd_spec *spec, const float *x0
                      const float *x_ref, const float *feet, const uint8_t *contacts, float *warm,
                      float *u0_all, int32_t *status_all, int32_t *iters_all,
                      int32_t max_stance_legs, void *stream);
+/* qloco_mgpu_solve with per-instance bodies (qloco_srbd_solve_model): `model`
+ * holds this rank's own `count` rows, in the order of its other shard inputs
+ * (device memory), or NULL = qloco_mgpu_solve. */
+int qloco_mgpu_solve_model(qloco_mgpu *h, const qloco_srbd_spec *spec, const float *x0,
+                           const float *x_ref, const float *feet, const uint8_t *contacts,
+                           float *warm, float *u0_all, int32_t *status_all, int32_t *iters_all,
+                           int32_t max_stance_legs, const qloco_srbd_model *model, void *stream);
 /* Releases the communicator and the buffers (NULL is a no-op). */
 int qloco_mgpu_destroy(qloco_mgpu *h);
 

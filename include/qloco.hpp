@@ -245,6 +245,14 @@ class ConvexMpcBatch {
   void solve_device(const float *x0, const float *x_ref, const float *feet,
                     const uint8_t *contacts, float *u0, int32_t *status, int32_t *iters);
   void reset();  // fresh solvers (the next call sets each one up again)
+  // Per-robot bodies (qloco_srbd_model, include/qloco.h): host_rows holds one
+  // row per robot of this object -- B rows, or this rank's shard_count rows in
+  // the multi-GPU form, in compute_grf's order -- copied to the device now;
+  // compute_grf and solve_device then solve robot b with its row's mass,
+  // inertia, mu and fz_min / fz_max in place of the spec's.  nullptr returns
+  // to the spec's body.  A robot with an invalid row gets status
+  // QLOCO_ERR_ARG and keeps its previous forces (the NaN guard).
+  void set_models(const qloco_srbd_model *host_rows);
   // settings / weights may be edited between calls; horizon and warm_start
   // size the device buffers and are fixed at construction (a changed value
   // throws qloco::Error on the next call)
@@ -257,6 +265,8 @@ class ConvexMpcBatch {
   int horizon_ = 0, warm_mode_ = 0;
   DeviceArena arena_;
   float *d_x0_, *d_xr_, *d_feet_, *d_u0_, *d_rec_ = nullptr;
+  qloco_srbd_model *d_model_ = nullptr;  // set_models' rows (allocated on first use)
+  bool use_model_ = false;
   uint8_t *d_ct_;
   int32_t *d_st_, *d_it_;
   // multi-GPU form

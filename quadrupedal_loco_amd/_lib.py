@@ -32,6 +32,12 @@ class SrbdSpec(C.Structure):
     ]
 
 
+class SrbdModel(C.Structure):
+    """Mirror of `qloco_srbd_model`: one robot's body, 64 bytes."""
+    _fields_ = [("mass", C.c_float), ("inertia", C.c_float * 9), ("mu", C.c_float),
+                ("fz_min", C.c_float), ("fz_max", C.c_float), ("reserved", C.c_float * 3)]
+
+
 class ForceParams(C.Structure):
     """Mirror of `qloco_force_params`."""
     _fields_ = [(k, C.c_double) for k in ("mass", "alpha", "beta", "gamma", "fz_max", "mu")]
@@ -144,6 +150,11 @@ SIGNATURES = {
                                       vp, vp, vp, i32, vp]),
     "qloco_srbd_solve_placed": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                           vp, vp, vp, i32, vp, vp]),
+    "qloco_srbd_model_from_spec": (C.c_int, [C.POINTER(SrbdSpec), i64, C.POINTER(SrbdModel)]),
+    "qloco_srbd_solve_model": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, i32, vp, vp, vp]),
+    "qloco_srbd_build_model": (C.c_int, [C.POINTER(SrbdSpec), i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                         vp, vp, vp, vp]),
     "qloco_srbd_place_bytes": (i64, [i64]),
     "qloco_srbd_place_order_host": (C.c_int, [i64, i64, i32, vp, vp]),
     "qloco_srbd_place_assign_host": (C.c_int, [i64, i64, vp]),
@@ -234,6 +245,8 @@ SIGNATURES = {
     "qloco_mgpu_init": (C.c_int, [vp, vp, i32, i32, i64, i32]),
     "qloco_mgpu_info": (C.c_int, [vp, vp, vp, vp, vp]),
     "qloco_mgpu_solve": (C.c_int, [vp, C.POINTER(SrbdSpec), vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "qloco_mgpu_solve_model": (C.c_int, [vp, C.POINTER(SrbdSpec), vp, vp, vp, vp, vp, vp, vp, vp, i32, vp,
+                                         vp]),
     "qloco_mgpu_destroy": (C.c_int, [vp]),
 }
 

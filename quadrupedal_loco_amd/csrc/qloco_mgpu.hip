@@ -266,6 +266,16 @@ extern "C" int qloco_mgpu_solve(qloco_mgpu *h, const qloco_srbd_spec *spec, cons
                                 const float *x_ref, const float *feet, const uint8_t *contacts,
                                 float *warm, float *u0_all, int32_t *status_all,
                                 int32_t *iters_all, int32_t max_stance_legs, void *stream) {
+  return qloco_mgpu_solve_model(h, spec, x0, x_ref, feet, contacts, warm, u0_all, status_all,
+                                iters_all, max_stance_legs, nullptr, stream);
+}
+
+extern "C" int qloco_mgpu_solve_model(qloco_mgpu *h, const qloco_srbd_spec *spec, const float *x0,
+                                      const float *x_ref, const float *feet,
+                                      const uint8_t *contacts, float *warm, float *u0_all,
+                                      int32_t *status_all, int32_t *iters_all,
+                                      int32_t max_stance_legs, const qloco_srbd_model *model,
+                                      void *stream) {
   if (!h || !spec || !u0_all) return QLOCO_ERR_ARG;
   int dev = -1;
   if (hipGetDevice(&dev) != hipSuccess || dev != h->device) {
@@ -276,10 +286,10 @@ extern "C" int qloco_mgpu_solve(qloco_mgpu *h, const qloco_srbd_spec *spec, cons
   const bool stats = status_all || iters_all;
   // 1. this rank's shard (its inputs are the caller's count instances)
   if (h->count > 0) {
-    const int rc = qloco_srbd_solve_ex(spec, h->count, x0, x_ref, feet, contacts, h->u0_local,
-                                       nullptr, stats ? h->status_local : nullptr,
-                                       stats ? h->iters_local : nullptr, nullptr, nullptr, warm,
-                                       max_stance_legs, stream);
+    const int rc = qloco_srbd_solve_model(spec, h->count, x0, x_ref, feet, contacts, h->u0_local,
+                                          nullptr, stats ? h->status_local : nullptr,
+                                          stats ? h->iters_local : nullptr, nullptr, nullptr, warm,
+                                          max_stance_legs, nullptr, model, stream);
     if (rc != QLOCO_OK) return rc;
   }
   // 2. one all-gather of the padded shard rows

@@ -566,7 +566,8 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   const int N = a.N;
   const float Nf = (float)N;
   const float dt = a.dt;
-  const float dtm = dt / a.mass, dt2m = dt * dt / a.mass;
+  const SrbdBody body = srbd_body(a, b);
+  const float dtm = dt / body.mass, dt2m = dt * dt / body.mass;
 
   // ---------------- 1. inputs -> LDS (one instance per block)
   srbd_load_inputs<NC>(a, S, b, t);
@@ -580,7 +581,11 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   const int n = 3 * nlegs;
   if (nlegs < a.leg_lo || nlegs > a.leg_hi) return;  // the other launch's instance
   if (nlegs > (W == 1 ? kW1Legs : w2_bucket_legs(C2))) {  // uniform
-    srbd_refuse_bad_size<NC>(a, b, t);
+    srbd_refuse<NC>(a, b, t, QLOCO_BAD_SIZE);
+    return;
+  }
+  if (a.model && srbd_body_bad(body)) {  // uniform; only a row can be (the spec's body is checked on the host)
+    srbd_refuse<NC>(a, b, t, QLOCO_ERR_ARG);
     return;
   }
   const int NP = 100 * N;
@@ -618,7 +623,7 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   f4v lo, hi;
   {
     float Ii[3][3], ba[3];
-    srbd_inertia_inv(cy, sy, a.inertia, Ii);
+    srbd_inertia_inv(cy, sy, body.inertia, Ii);
     // this lane's B_d column (rows 6..8) and E = dt A_c B_d column (rows 0..2)
     srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, step, leg), comp, dt, R00, R01,
                    R10, R11, step, valid, ba, lo, hi);
@@ -655,8 +660,8 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
   const bool xy = comp < 2;
   // A entries (ra0, ra1, rz0, rz1) of the two slots: LDS-resident from here on
   // (Ruiz scales them in place; registers would carry them across the setup)
-  S.arz[t] = (f4v){valid ? 1.0f : 0.0f, (valid && xy) ? 1.0f : 0.0f, (valid && xy) ? a.mu : 0.0f,
-                   (valid && xy) ? -a.mu : 0.0f};
+  S.arz[t] = (f4v){valid ? 1.0f : 0.0f, (valid && xy) ? 1.0f : 0.0f, (valid && xy) ? body.mu : 0.0f,
+                   (valid && xy) ? -body.mu : 0.0f};
   float rE0 = 1.0f, rE1 = 1.0f, Dr = 1.0f, cs = 1.0f;
   S.aux[0][t] = r2v;
   S.pair[t] = 4 * step + leg;
@@ -824,8 +829,8 @@ __device__ __forceinline__ void srbd_solve_one(const SrbdArgs &a, SrbdLds<W, NM>
       // stance pair, 0 on the swing pairs the literal full QP keeps (computed
       // here, not at entry: kept live across the setup they spilled)
       const float cflag = valid ? (float)S.ct[S.pair[opaque_tid()]] : 0.0f;
-      const float rl0 = !valid ? 0.0f : (xy ? 0.0f : a.fz_min * cflag);
-      const float ru0 = !valid ? 0.0f : (xy ? INFINITY : a.fz_max * cflag);
+      const float rl0 = !valid ? 0.0f : (xy ? 0.0f : body.fz_min * cflag);
+      const float ru0 = !valid ? 0.0f : (xy ? INFINITY : body.fz_max * cflag);
       const float lh0 = rl0 * rE0, uh0 = ru0 * rE0;
       // slot 1: (-inf, 0] on x/y lanes (E scaling keeps 0 and inf), inert [0, 0] elsewhere
       const float lh1 = (valid && xy) ? -INFINITY : 0.0f, uh1 = 0.0f;
@@ -1424,12 +1429,27 @@ extern "C" int qloco_srbd_route(const qloco_srbd_spec *spec) {
   return srbd_route_of(a);
 }
 
-extern "C" int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
-                                       const float *x_ref, const float *feet,
-                                       const uint8_t *contacts, float *u0, float *u,
-                                       int32_t *status, int32_t *iters, int32_t *rho_updates,
-                                       float *obj, float *warm, int32_t max_stance_legs,
-                                       int32_t *place, void *stream) {
+extern "C" int qloco_srbd_model_from_spec(const qloco_srbd_spec *spec, int64_t count,
+                                          qloco_srbd_model *rows) {
+  if (!spec || count < 0 || (count > 0 && !rows)) return QLOCO_ERR_ARG;
+  qloco_srbd_model m;
+  memset(&m, 0, sizeof(m));
+  m.mass = spec->mass;
+  for (int k = 0; k < 9; ++k) m.inertia[k] = spec->inertia[k];
+  m.mu = spec->mu;
+  m.fz_min = spec->fz_min;
+  m.fz_max = spec->fz_max;
+  for (int64_t b = 0; b < count; ++b) rows[b] = m;
+  return QLOCO_OK;
+}
+
+extern "C" int qloco_srbd_solve_model(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                      const float *x_ref, const float *feet,
+                                      const uint8_t *contacts, float *u0, float *u,
+                                      int32_t *status, int32_t *iters, int32_t *rho_updates,
+                                      float *obj, float *warm, int32_t max_stance_legs,
+                                      int32_t *place, const qloco_srbd_model *model,
+                                      void *stream) {
   if (!spec || batch < 0) return QLOCO_ERR_ARG;
   if (spec->horizon < 1 || spec->horizon > kMaxN) return QLOCO_BAD_SIZE;
   if (batch == 0) return QLOCO_OK;
@@ -1457,6 +1477,7 @@ extern "C" int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batc
   a.status = status;
   a.iters = iters;
   a.rho_updates = rho_updates;
+  a.model = reinterpret_cast<const float *>(model);
   // Kernel per instance class: <= 21 stance legs one-wave workgroups,
   // 22..42 two-wave workgroups, 43..80 the wide kernel (qloco_srbd_big.inc).
   // A batch that may hold several classes (the caller's maximum, or 4N when
@@ -1599,6 +1620,16 @@ extern "C" int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batc
   }
   QLOCO_HIP_CHECK(hipGetLastError(), "srbd_admm_kernel launch");
   return QLOCO_OK;
+}
+
+extern "C" int qloco_srbd_solve_placed(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                       const float *x_ref, const float *feet,
+                                       const uint8_t *contacts, float *u0, float *u,
+                                       int32_t *status, int32_t *iters, int32_t *rho_updates,
+                                       float *obj, float *warm, int32_t max_stance_legs,
+                                       int32_t *place, void *stream) {
+  return qloco_srbd_solve_model(spec, batch, x0, x_ref, feet, contacts, u0, u, status, iters,
+                                rho_updates, obj, warm, max_stance_legs, place, nullptr, stream);
 }
 
 extern "C" int qloco_srbd_solve_ex(const qloco_srbd_spec *spec, int64_t batch, const float *x0,

@@ -167,7 +167,8 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   const int N = a.N;
   const float Nf = (float)N;
   const float dt = a.dt;
-  const float dtm = dt / a.mass, dt2m = dt * dt / a.mass;
+  const SrbdBody body = srbd_body(a, b);
+  const float dtm = dt / body.mass, dt2m = dt * dt / body.mass;
 
   // ---------------- 1. inputs -> LDS, 2. stance enumeration (srbd_solve_one)
   srbd_load_inputs<kBigThreads>(a, S, b, t);
@@ -178,7 +179,11 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   const int n = 3 * nlegs;
   if (nlegs < a.leg_lo || nlegs > a.leg_hi) return;  // another launch's instance
   if (nlegs > big_bucket_legs(HC)) {  // uniform
-    srbd_refuse_bad_size<kBigThreads>(a, b, t);
+    srbd_refuse<kBigThreads>(a, b, t, QLOCO_BAD_SIZE);
+    return;
+  }
+  if (a.model && srbd_body_bad(body)) {  // uniform; only a row can be
+    srbd_refuse<kBigThreads>(a, b, t, QLOCO_ERR_ARG);
     return;
   }
   const int NP = 100 * N;
@@ -210,7 +215,7 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
   f4v lo, hi;
   {
     float Ii[3][3], ba[3];
-    srbd_inertia_inv(cy, sy, a.inertia, Ii);
+    srbd_inertia_inv(cy, sy, body.inertia, Ii);
     srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, step, leg), comp, dt, R00, R01,
                    R10, R11, step, valid, ba, lo, hi);
     if (h == 0) {
@@ -243,14 +248,14 @@ void srbd_admm_big_kernel(const SrbdArgs a) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {  // [1,0,mu] >= 0, [1,0,-mu] <= 0, [0,1,mu] >= 0, [0,1,-mu] <= 0
       L.ao[i] = on;
-      L.az[i] = valid ? ((i & 1) ? -a.mu : a.mu) : 0.0f;
+      L.az[i] = valid ? ((i & 1) ? -body.mu : body.mu) : 0.0f;
       L.lo[i] = valid ? ((i & 1) ? -INFINITY : 0.0f) : 0.0f;
       L.up[i] = valid ? ((i & 1) ? 0.0f : INFINITY) : 0.0f;
     }
     L.ao[4] = on;  // fz in [fz_min * c, fz_max * c]: c = 0 on the literal QP's swing pairs
     const float cflag = valid ? (float)S.ct[4 * step + leg] : 0.0f;
-    L.lo[4] = valid ? a.fz_min * cflag : 0.0f;
-    L.up[4] = valid ? a.fz_max * cflag : 0.0f;
+    L.lo[4] = valid ? body.fz_min * cflag : 0.0f;
+    L.up[4] = valid ? body.fz_max * cflag : 0.0f;
 #pragma unroll
     for (int i = 0; i < 5; ++i) {
       L.E[i] = 1.0f;

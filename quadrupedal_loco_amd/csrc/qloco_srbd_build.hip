@@ -20,13 +20,15 @@ namespace qloco {
 
 struct BuildArgs {
   int N, feet_per_step, contacts_per_step;
-  float dt, mass, mu, fz_min, fz_max;
+  float dt, mass;
   float inertia[9];
+  float mu, fz_min, fz_max;
   float q2[13], r2[12];
   int64_t batch;
   const float *x0, *xref, *feet;
   const uint8_t *contacts;
   float *H, *g, *lb, *ub, *Aqp, *Bqp;
+  const float *model;  // per-instance bodies (qloco_srbd_build_model) or NULL
 };
 
 __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
@@ -40,6 +42,7 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
   const int64_t b = blockIdx.x;
   const int N = a.N, nx = 13 * N, nu = 12 * N, nc = 20 * N;
   const float dt = a.dt;
+  const SrbdBody body = srbd_body(a, b);
   if (t == 0) {
 #pragma unroll
     for (int k = 0; k < 13; ++k) q2[k] = a.q2[k];
@@ -58,10 +61,10 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
     const int leg = col / 3, comp = col - 3 * leg;
     float Ii[3][3], w[3];
     f4v lo, hi;  // lo = {w, E row 0}, hi = {E rows 1, 2, ..}
-    srbd_inertia_inv(cy, sy, a.inertia, Ii);
+    srbd_inertia_inv(cy, sy, body.inertia, Ii);
     srbd_bd_column(Ii, srbd_foot(a.feet, b, N, a.feet_per_step, k, leg), comp, dt, Rm[0][0],
                    Rm[0][1], Rm[1][0], Rm[1][1], k, true, w, lo, hi);
-    const float vm = dt / a.mass;
+    const float vm = dt / body.mass;
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
       Bd[k][r][col] = w[r];
@@ -123,8 +126,8 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
     for (int idx = t; idx < nc; idx += 256) {
       const int k = idx / 20, w = idx - 20 * k, leg = w / 5, row = w - 5 * leg;
       const float cf = a.contacts[b * nct + (a.contacts_per_step ? 4 * k + leg : leg)] ? 1.0f : 0.0f;
-      const float lo[5] = {0.f, -1e30f, 0.f, -1e30f, a.fz_min * cf};
-      const float hi[5] = {1e30f, 0.f, 1e30f, 0.f, a.fz_max * cf};
+      const float lo[5] = {0.f, -1e30f, 0.f, -1e30f, body.fz_min * cf};
+      const float hi[5] = {1e30f, 0.f, 1e30f, 0.f, body.fz_max * cf};
       a.lb[b * nc + idx] = lo[row];
       a.ub[b * nc + idx] = hi[row];
     }
@@ -165,10 +168,11 @@ __global__ __launch_bounds__(256) void srbd_build_kernel(const BuildArgs a) {
 
 using namespace qloco;
 
-extern "C" int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
-                                const float *x_ref, const float *feet, const uint8_t *contacts,
-                                float *H, float *g, float *lb, float *ub, float *Aqp, float *Bqp,
-                                void *stream) {
+extern "C" int qloco_srbd_build_model(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                      const float *x_ref, const float *feet,
+                                      const uint8_t *contacts, float *H, float *g, float *lb,
+                                      float *ub, float *Aqp, float *Bqp,
+                                      const qloco_srbd_model *model, void *stream) {
   if (!spec || batch < 0) return QLOCO_ERR_ARG;
   if (spec->horizon < 1 || spec->horizon > kMaxN) return QLOCO_BAD_SIZE;
   if (batch == 0) return QLOCO_OK;
@@ -198,7 +202,16 @@ extern "C" int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, cons
   a.ub = ub;
   a.Aqp = Aqp;
   a.Bqp = Bqp;
+  a.model = reinterpret_cast<const float *>(model);
   hipLaunchKernelGGL(srbd_build_kernel, dim3((unsigned)batch), dim3(256), 0, (hipStream_t)stream, a);
   QLOCO_HIP_CHECK(hipGetLastError(), "srbd_build_kernel launch");
   return QLOCO_OK;
+}
+
+extern "C" int qloco_srbd_build(const qloco_srbd_spec *spec, int64_t batch, const float *x0,
+                                const float *x_ref, const float *feet, const uint8_t *contacts,
+                                float *H, float *g, float *lb, float *ub, float *Aqp, float *Bqp,
+                                void *stream) {
+  return qloco_srbd_build_model(spec, batch, x0, x_ref, feet, contacts, H, g, lb, ub, Aqp, Bqp,
+                                nullptr, stream);
 }

@@ -57,6 +57,11 @@ struct SrbdArgs {
   float lit_sq;   // 1 / sqrt(q_omega): S = Rz' / sqrt(q_omega)
   float lit_gmx;  // max diag G^-1
   alignas(16) float lit_gtab[kLitN * kLitN * 6];  // LitLds<1>::gtab's layout
+  // per-instance bodies (qloco_srbd_solve_model): batch rows of 16 floats in
+  // qloco_srbd_model's layout, or NULL: mass, inertia, mu and fz_* above.
+  // Read through srbd_body (qloco_srbd_model.hpp) only.  Last, so that every
+  // other field keeps its offset in the kernel-argument segment.
+  const float *model;
 };
 
 // The fields a spec determines; the batch, the buffers and the launch's
@@ -238,6 +243,7 @@ static_assert(offsetof(SrbdArgs, lit_gtab) % 16 == 0, "lit_gtab is read in 16-by
 
 // place: the caller's placement state or NULL; simds: spec.reserved[1]
 // (0 = four per compute unit of the current device)
+// a.model set: the instantiations that read the rows
 int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hipStream_t stream);
 int srbd_place_launch(int32_t *place, int64_t batch, int simds, int check_termination,
                       hipStream_t stream);

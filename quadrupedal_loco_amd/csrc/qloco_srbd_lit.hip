@@ -376,7 +376,9 @@ __device__ __forceinline__ void lit_invert2(LitLds<2> &S, int wv, int nc0, int n
 
 // WS: a warm-start mode (1 or 2) may be set (the persistent record of
 // DESIGN.md §3c, literal semantics: the update path on every call).
-template <int W, bool WS>
+// MR: the call carries model rows (a.model); false compiles to the code of a
+// kernel that knows no rows.
+template <int W, bool WS, bool MR>
 __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, const int64_t b) {
   constexpr int NS = LitLds<W>::NS, NT = LitLds<W>::NT;
   const int lane = W == 1 ? (int)threadIdx.x : (int)(threadIdx.x & 63);
@@ -385,7 +387,26 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
   const int N = a.N;
   const float Nf = (float)N;
   const float dt = a.dt;
-  const float dtm = dt / a.mass, dt2m = dt * dt / a.mass;
+  // with rows, a phase loads the values it needs again (an opaque index: the
+  // loads are not merged with the first ones and held in SGPRs across the
+  // setup -- the one-wave kernel has none to spare)
+  SrbdBodyAt<MR> body{a};
+  auto load_body = [&] {
+    if constexpr (MR) {
+      int64_t bb = b;
+      asm volatile("" : "+s"(bb));
+      body.row = srbd_body(a, bb);
+    }
+  };
+  if constexpr (MR) {
+    body.row = srbd_body(a, b);
+    if (srbd_body_bad(body.row)) {  // uniform, before the first barrier and the first write
+      // (a thread index of its own: none is kept for it across the solve)
+      srbd_refuse<64 * W>(a, b, W == 1 ? fresh_lane() : opaque_tid(), QLOCO_ERR_ARG);
+      return;
+    }
+  }
+  const float dtm = dt / body.mass(), dt2m = dt * dt / body.mass();
   // this wave's steps: [so, so + Nw) (W = 1: all N)
   const int H = W == 1 ? N : (N + 1) / 2;
   const int so = W == 1 ? 0 : wv * H;
@@ -439,7 +460,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
     }
   }
   float Ii[3][3];
-  srbd_inertia_inv(cy, sy, a.inertia, Ii);
+  srbd_inertia_inv(cy, sy, body.inertia(), Ii);
   // per slot: the variable, its B_d column (omega rows: ba) and E column
   const int comp = lane % 3;
   const bool xy = comp < 2;
@@ -537,15 +558,16 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
 
   // ---------------- 4. constraint rows owned by each slot (ConvexMpc.cpp:47-59, :227-249)
   float ra0[2], ra1[2], rz0[2], rz1[2], rl0[2], ru0[2];
+  load_body();
 #pragma unroll
   for (int h = 0; h < 2; ++h) {
     ra0[h] = valid[h] ? 1.0f : 0.0f;
     ra1[h] = (valid[h] && xy) ? 1.0f : 0.0f;
-    rz0[h] = (valid[h] && xy) ? a.mu : 0.0f;
-    rz1[h] = (valid[h] && xy) ? -a.mu : 0.0f;
+    rz0[h] = (valid[h] && xy) ? body.mu() : 0.0f;
+    rz1[h] = (valid[h] && xy) ? -body.mu() : 0.0f;
     const float cflag = valid[h] ? S.ctf[4 * step[h] + leg[h]] : 0.0f;
-    rl0[h] = !valid[h] ? 0.0f : (xy ? 0.0f : a.fz_min * cflag);
-    ru0[h] = !valid[h] ? 0.0f : (xy ? INFINITY : a.fz_max * cflag);
+    rl0[h] = !valid[h] ? 0.0f : (xy ? 0.0f : body.fz_min() * cflag);
+    ru0[h] = !valid[h] ? 0.0f : (xy ? INFINITY : body.fz_max() * cflag);
   }
 
   // ---------------- 5. modified Ruiz equilibration (OSQP scaling.c), P rows
@@ -772,7 +794,8 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
     S.sc[wv].oma = 1.0f - a.alpha;
     S.sc[wv].sigma = a.sigma;
     S.sc[wv].dtm = dtm;
-    S.sc[wv].zlo = a.fz_max > 0.0f ? a.fz_min / a.fz_max : 0.0f;
+    load_body();
+    S.sc[wv].zlo = body.fz_max() > 0.0f ? body.fz_min() / body.fz_max() : 0.0f;
     const int ctm = a.check_termination;
     S.sc[wv].ctm = ctm;
     S.sc[wv].interval = (a.adaptive_rho && a.rho_interval == 0) ? (ctm ? 4 * ctm : 100)
@@ -1630,31 +1653,53 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
   }
 }
 
+// One instance per workgroup.  srbd_lit_kernel / srbd_lit2_kernel are the
+// kernels of a call without model rows (MR = false in srbd_lit_one),
+// srbd_lit_rows_kernel / srbd_lit2_rows_kernel those of a call with rows; a
+// pair shares its body as text, so the first two stay the kernels they were.
+//
+// One wave: the placement state's order (qloco_srbd_place.hpp) once it is
+// ready for this batch: which workgroup solves an instance, never what it
+// computes or where its outputs go.  The workgroup's rank is place_assign's
+// (DESIGN.md §3r): uniform scalar arithmetic and two uniform loads
+#define QL_LIT_KERNEL_BODY(MR)                                                                             \
+  __shared__ __attribute__((aligned(16))) LitLds<1> S;                                                     \
+  int64_t i = blockIdx.x;                                                                                  \
+  if (a.order && a.hint[-kPlaceHeader] == a.batch) {                                                       \
+    const int64_t at = place_position(place_assign(i, a.batch, a.place_simds), a.batch, a.place_simds);    \
+    if (at < 0 || at >= a.batch) return;                                                                   \
+    i = a.order[at];                                                                                       \
+  }                                                                                                        \
+  if (i < 0 || i >= a.batch) return;                                                                       \
+  srbd_lit_one<1, WS, MR>(a, S, i)
+#define QL_LIT2_KERNEL_BODY(MR)                           \
+  __shared__ __attribute__((aligned(16))) LitLds<2> S;    \
+  const int64_t i = blockIdx.x;                           \
+  if (i >= a.batch) return;                               \
+  srbd_lit_one<2, WS, MR>(a, S, i)
+
 template <bool WS>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLitWpe)))
 void srbd_lit_kernel(const SrbdArgs a) {
-  __shared__ __attribute__((aligned(16))) LitLds<1> S;
-  // the placement state's order (qloco_srbd_place.hpp) once it is ready for
-  // this batch: which workgroup solves an instance, never what it computes
-  // or where its outputs go.  The workgroup's rank is place_assign's (DESIGN.md
-  // §3r): uniform scalar arithmetic and two uniform loads
-  int64_t i = blockIdx.x;
-  if (a.order && a.hint[-kPlaceHeader] == a.batch) {
-    const int64_t at = place_position(place_assign(i, a.batch, a.place_simds), a.batch, a.place_simds);
-    if (at < 0 || at >= a.batch) return;
-    i = a.order[at];
-  }
-  if (i < 0 || i >= a.batch) return;
-  srbd_lit_one<1, WS>(a, S, i);
+  QL_LIT_KERNEL_BODY(false);
+}
+
+template <bool WS>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kLitWpe)))
+void srbd_lit_rows_kernel(const SrbdArgs a) {
+  QL_LIT_KERNEL_BODY(true);
 }
 
 template <bool WS>
 __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(kLit2Wpe)))
 void srbd_lit2_kernel(const SrbdArgs a) {
-  __shared__ __attribute__((aligned(16))) LitLds<2> S;
-  const int64_t i = blockIdx.x;
-  if (i >= a.batch) return;
-  srbd_lit_one<2, WS>(a, S, i);
+  QL_LIT2_KERNEL_BODY(false);
+}
+
+template <bool WS>
+__global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(kLit2Wpe)))
+void srbd_lit2_rows_kernel(const SrbdArgs a) {
+  QL_LIT2_KERNEL_BODY(true);
 }
 
 // SIMDs of the current device (four per compute unit), asked once per device
@@ -1676,10 +1721,12 @@ static int device_simds(int *simds) {
 
 int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hipStream_t stream) {
   const dim3 grid((unsigned)a.batch);
+  const bool rows = a.model != nullptr;
   if (a.N < 1 || a.N > kLitN2) return QLOCO_BAD_SIZE;
   if (a.N <= kLitN) {
     if (warm) {
-      hipLaunchKernelGGL(srbd_lit_kernel<true>, grid, dim3(64), 0, stream, a);
+      hipLaunchKernelGGL((rows ? srbd_lit_rows_kernel<true> : srbd_lit_kernel<true>), grid, dim3(64), 0,
+                         stream, a);
     } else {
       // cold solves of a batch that is resident at once but fills more than
       // one wave slot per SIMD: the launch ends with its most loaded SIMD, so
@@ -1698,16 +1745,19 @@ int srbd_lit_launch(const SrbdArgs &a, bool warm, int32_t *place, int simds, hip
         ap.order = place + kPlaceHeader + a.batch;
         ap.place_simds = simds;
       }
-      hipLaunchKernelGGL(srbd_lit_kernel<false>, grid, dim3(64), 0, stream, ap);
+      hipLaunchKernelGGL((rows ? srbd_lit_rows_kernel<false> : srbd_lit_kernel<false>), grid, dim3(64), 0,
+                         stream, ap);
       QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit_kernel launch");
       if (placed) return srbd_place_launch(place, a.batch, simds, a.check_termination, stream);
     }
     QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit_kernel launch");
   } else {
     if (warm)
-      hipLaunchKernelGGL(srbd_lit2_kernel<true>, grid, dim3(128), 0, stream, a);
+      hipLaunchKernelGGL((rows ? srbd_lit2_rows_kernel<true> : srbd_lit2_kernel<true>), grid, dim3(128), 0,
+                         stream, a);
     else
-      hipLaunchKernelGGL(srbd_lit2_kernel<false>, grid, dim3(128), 0, stream, a);
+      hipLaunchKernelGGL((rows ? srbd_lit2_rows_kernel<false> : srbd_lit2_kernel<false>), grid, dim3(128), 0,
+                         stream, a);
     QLOCO_HIP_CHECK(hipGetLastError(), "srbd_lit2_kernel launch");
   }
   return QLOCO_OK;

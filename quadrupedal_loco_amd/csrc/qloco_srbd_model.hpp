@@ -5,7 +5,7 @@
 // wave kernel and the wide kernel share.  Leaf functions only: no LDS layout
 // and no kernel structure in a signature; the prologue functions take the
 // LDS struct as a template parameter and leave every barrier to the caller.
-// DESIGN.md §3p has the per-kernel record.
+// DESIGN.md §3p has the per-kernel record; §3s the per-instance body (srbd_body).
 #pragma once
 
 #include <math.h>
@@ -13,6 +13,73 @@
 #include "qloco_srbd_core.hpp"
 
 namespace qloco {
+
+// The body of one instance: the five quantities of qloco_srbd_model
+struct SrbdBody {
+  float mass;
+  float inertia[9];
+  float mu, fz_min, fz_max;
+};
+
+// Instance b's body: its row of a.model (qloco_srbd_model, 16 floats) when
+// the call carries rows, the kernel-argument fields otherwise.  b is
+// wave-uniform in every SRBD kernel (a blockIdx expression, or a uniform load
+// from the class list / the placement order), so the row arrives by scalar
+// loads: the index through readfirstlane, the row read through the constant
+// address space (the rows are never written during a call), and the values
+// stay in SGPRs like the kernel arguments they replace.  The 13 floats are
+// adjacent dword loads of a 64-byte-aligned row, merged by the compiler; a
+// caller that uses some of them gets those loads alone.
+template <class Args>
+__device__ __forceinline__ SrbdBody srbd_body(const Args &a, int64_t b) {
+  SrbdBody m;
+  if (a.model) {
+    typedef const __attribute__((address_space(4))) float *row_ptr;
+    const int64_t bu = ((int64_t)__builtin_amdgcn_readfirstlane((int)(b >> 32)) << 32) |
+                       (uint32_t)__builtin_amdgcn_readfirstlane((int)b);
+    const row_ptr r = (row_ptr)(uintptr_t)__builtin_assume_aligned(a.model + 16 * bu, 64);
+    m.mass = r[0];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) m.inertia[k] = r[1 + k];
+    m.mu = r[10];
+    m.fz_min = r[11];
+    m.fz_max = r[12];
+  } else {
+    m.mass = a.mass;
+#pragma unroll
+    for (int k = 0; k < 9; ++k) m.inertia[k] = a.inertia[k];
+    m.mu = a.mu;
+    m.fz_min = a.fz_min;
+    m.fz_max = a.fz_max;
+  }
+  return m;
+}
+
+// The same quantities for a kernel with one instantiation per kind of call
+// (the literal kernels): ROWS = true reads the row srbd_body loaded, ROWS =
+// false the kernel-argument field itself, at the place of use, so that
+// instantiation compiles as a kernel that knows no rows does.
+template <bool ROWS>
+struct SrbdBodyAt {
+  const SrbdArgs &a;
+  SrbdBody row;  // ROWS only
+  __device__ __forceinline__ float mass() const { return ROWS ? row.mass : a.mass; }
+  __device__ __forceinline__ const float *inertia() const { return ROWS ? row.inertia : a.inertia; }
+  __device__ __forceinline__ float mu() const { return ROWS ? row.mu : a.mu; }
+  __device__ __forceinline__ float fz_min() const { return ROWS ? row.fz_min : a.fz_min; }
+  __device__ __forceinline__ float fz_max() const { return ROWS ? row.fz_max : a.fz_max; }
+};
+
+// A row the solve refuses (qloco_srbd_solve_model): one of its 13 values is
+// not finite, or mass <= 0.  Asked of rows only: the kernel-argument body is
+// validated on the host, as before.
+__device__ __forceinline__ bool srbd_body_bad(const SrbdBody &m) {
+  bool ok = m.mass > 0.0f && isfinite(m.mass) && isfinite(m.mu) && isfinite(m.fz_min) &&
+            isfinite(m.fz_max);
+#pragma unroll
+  for (int k = 0; k < 9; ++k) ok = ok && isfinite(m.inertia[k]);
+  return !ok;
+}
 
 // World inverse inertia (Rz I Rz')^-1 with the yaw "rotation"
 // R = [[c,s,0],[-s,c,0],[0,0,1]] that overwrites root_rot_mat
@@ -147,17 +214,20 @@ __device__ __forceinline__ void srbd_enumerate_stance(const SrbdArgs &a, Lds &S,
   }
 }
 
-// The result of an instance with more stance legs than the kernel holds (the
-// caller's max_stance_legs was too small): QLOCO_BAD_SIZE and NaN outputs
+// The result of an instance the kernel does not solve: the code as its status
+// and NaN outputs.  QLOCO_BAD_SIZE: more stance legs than the kernel holds
+// (the caller's max_stance_legs was too small); QLOCO_ERR_ARG: an invalid
+// model row (srbd_body_bad)
 template <int NT>
-__device__ __forceinline__ void srbd_refuse_bad_size(const SrbdArgs &a, int64_t b, int t) {
+__device__ __forceinline__ void srbd_refuse(const SrbdArgs &a, int64_t b, int t, int code) {
   const int N = a.N;
   if (t < 12) a.u0[b * 12 + t] = NAN;
   if (a.u)
     for (int k = t; k < 12 * N; k += NT) a.u[b * 12 * N + k] = NAN;
   if (t == 0) {
-    if (a.status) a.status[b] = QLOCO_BAD_SIZE;
+    if (a.status) a.status[b] = code;
     if (a.iters) a.iters[b] = 0;
+    if (a.hint) a.hint[b] = 0;  // placement state (the one-wave literal kernel)
     if (a.rho_updates) a.rho_updates[b] = 0;
     if (a.obj) a.obj[b] = NAN;
   }

@@ -458,6 +458,14 @@ void ConvexMpcBatch::reset() {
          "hipMemsetAsync");
 }
 
+void ConvexMpcBatch::set_models(const qloco_srbd_model *host_rows) {
+  use_model_ = host_rows != nullptr;
+  if (!host_rows) return;
+  if (!d_model_) d_model_ = dalloc<qloco_srbd_model>(arena_, (size_t)batch_);
+  arena_.upload(d_model_, host_rows, sizeof(qloco_srbd_model) * (size_t)batch_);
+  arena_.sync();  // the caller's rows may go away after the call
+}
+
 void ConvexMpcBatch::solve_device(const float *x0, const float *x_ref, const float *feet,
                                   const uint8_t *contacts, float *u0, int32_t *st, int32_t *it) {
   check_spec();
@@ -465,9 +473,10 @@ void ConvexMpcBatch::solve_device(const float *x0, const float *x_ref, const flo
     throw Error("ConvexMpcBatch::solve_device: a multi-GPU object solves through compute_grf "
                 "(or qloco_mgpu_solve directly)", QLOCO_ERR_ARG);
   const int32_t legs = 4 * horizon_;  // constant contacts over the horizon: 4N worst case
-  abi_ok(qloco_srbd_solve_ex(&spec, batch_, x0, x_ref, feet, contacts, u0, nullptr, st, it,
-                             nullptr, nullptr, d_rec_, legs, arena_.stream()),
-         "qloco_srbd_solve_ex");
+  abi_ok(qloco_srbd_solve_model(&spec, batch_, x0, x_ref, feet, contacts, u0, nullptr, st, it,
+                                nullptr, nullptr, d_rec_, legs, nullptr,
+                                use_model_ ? d_model_ : nullptr, arena_.stream()),
+         "qloco_srbd_solve_model");
 }
 
 void ConvexMpcBatch::compute_grf(const A1MpcState *s, double *forces) {
@@ -524,9 +533,10 @@ void ConvexMpcBatch::compute_grf(const A1MpcState *s, double *forces) {
   arena_.upload(d_feet_, feet.data(), sizeof(float) * B * 12);
   arena_.upload(d_ct_, ct.data(), B * 4);
   if (mg_) {  // this rank's shard, then one all-gather of every robot's u0
-    abi_ok(qloco_mgpu_solve(mg_, &spec, d_x0_, d_xr_, d_feet_, d_ct_, d_rec_, d_u0_all_, d_st_all_,
-                            d_it_all_, maxlegs, arena_.stream()),
-           "qloco_mgpu_solve");
+    abi_ok(qloco_mgpu_solve_model(mg_, &spec, d_x0_, d_xr_, d_feet_, d_ct_, d_rec_, d_u0_all_,
+                                  d_st_all_, d_it_all_, maxlegs, use_model_ ? d_model_ : nullptr,
+                                  arena_.stream()),
+           "qloco_mgpu_solve_model");
     const size_t T = (size_t)total_;
     std::vector<float> ua(T * 12);
     std::vector<int32_t> sa(T), ia(T);
@@ -552,9 +562,10 @@ void ConvexMpcBatch::compute_grf(const A1MpcState *s, double *forces) {
     }
     return;
   }
-  abi_ok(qloco_srbd_solve_ex(&spec, batch_, d_x0_, d_xr_, d_feet_, d_ct_, d_u0_, nullptr, d_st_,
-                             d_it_, nullptr, nullptr, d_rec_, maxlegs, arena_.stream()),
-         "qloco_srbd_solve_ex");
+  abi_ok(qloco_srbd_solve_model(&spec, batch_, d_x0_, d_xr_, d_feet_, d_ct_, d_u0_, nullptr, d_st_,
+                                d_it_, nullptr, nullptr, d_rec_, maxlegs, nullptr,
+                                use_model_ ? d_model_ : nullptr, arena_.stream()),
+         "qloco_srbd_solve_model");
   std::vector<float> u0(B * 12);
   arena_.download(u0.data(), d_u0_, sizeof(float) * B * 12);
   arena_.download(status.data(), d_st_, sizeof(int32_t) * B);

@@ -84,7 +84,10 @@ class MgpuSolver:
         self.status_all = torch.empty(self.total, dtype=torch.int32, device=dev)
         self.iters_all = torch.empty(self.total, dtype=torch.int32, device=dev)
 
-    def solve(self, x0, x_ref, feet, contacts, stats=False, max_legs=0, warm=None, stream=None):
+    def solve(self, x0, x_ref, feet, contacts, stats=False, max_legs=0, warm=None, stream=None,
+              model=None):
+        """model: this rank's own (count, 16) rows of srbd.model_rows(), laid
+        out like its other shard inputs (qloco_mgpu_solve_model), or None."""
         import torch
         from .srbd import check_inputs
         N = self.spec.horizon
@@ -92,16 +95,19 @@ class MgpuSolver:
             raise ValueError("this rank owns %d instances, got %d" % (self.count, x0.shape[0]))
         # the checks BatchedConvexMpc.solve runs, on the handle's device: a CPU,
         # float64 or non-contiguous tensor is refused before the C call
-        check_inputs(self.spec, x0, x_ref, feet, contacts, warm=warm, device=self.device)
+        check_inputs(self.spec, x0, x_ref, feet, contacts, warm=warm, device=self.device, model=model)
         self.spec.feet_per_step = 1 if feet.shape[1] == 12 * N and N > 1 else 0
         self.spec.contacts_per_step = 1 if contacts.shape[1] == 4 * N and N > 1 else 0
         if stream is None:
             stream = torch.cuda.current_stream().cuda_stream
-        check(lib().qloco_mgpu_solve(
-            self._h, C.byref(self.spec), ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts), ptr(warm),
-            ptr(self.u0_all), ptr(self.status_all) if stats else None,
-            ptr(self.iters_all) if stats else None, int(max_legs), C.c_void_p(stream)),
-            "qloco_mgpu_solve")
+        head = (self._h, C.byref(self.spec), ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts), ptr(warm),
+                ptr(self.u0_all), ptr(self.status_all) if stats else None,
+                ptr(self.iters_all) if stats else None, int(max_legs))
+        if model is None:
+            check(lib().qloco_mgpu_solve(*head, C.c_void_p(stream)), "qloco_mgpu_solve")
+        else:
+            check(lib().qloco_mgpu_solve_model(*head, ptr(model), C.c_void_p(stream)),
+                  "qloco_mgpu_solve_model")
         return self.u0_all
 
     def close(self):

@@ -18,7 +18,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import SrbdSpec, check, lib, ptr
+from ._lib import SrbdModel, SrbdSpec, check, lib, ptr
 
 GAITS = {"trot": 0, "pace": 1, "biped": 1, "mixed": 2, "stance": 3}
 PLACE_STATES = 8  # placement states a BatchedConvexMpc keeps (one per batch, device, stream)
@@ -104,6 +104,39 @@ def control_loop_sequence(seed, horizon, count, ticks, gait="trot", switch_every
     return seq
 
 
+MODEL_COLUMNS = {"mass": (0, 1), "inertia": (1, 10), "mu": (10, 11), "fz_min": (11, 12),
+                 "fz_max": (12, 13)}
+
+
+def model_rows(batch, spec=None, **columns):
+    """Per-robot bodies for solve(model=) / build(model=): a (B, 16) float32
+    host array in qloco_srbd_model's layout (mass | inertia[9] col-major | mu |
+    fz_min | fz_max | 3 reserved zeros), every row filled from `spec` (default:
+    the Go1 defaults) by qloco_srbd_model_from_spec.  `columns` then overwrite
+    whole columns: mass, mu, fz_min, fz_max as a scalar or (B,); inertia as 9
+    values (or 3 x 3, read col-major) for every robot or (B, 9).  Edit single
+    rows in place, then move the array to the device
+    (torch.from_numpy(rows).to(dev))."""
+    B = int(batch)
+    rows = np.zeros((B, 16), np.float32)
+    sp = spec if spec is not None else default_spec()
+    check(lib().qloco_srbd_model_from_spec(C.byref(sp), B, rows.ctypes.data_as(C.POINTER(SrbdModel))),
+          "qloco_srbd_model_from_spec")
+    for name, v in columns.items():
+        if name not in MODEL_COLUMNS:
+            raise ValueError("model_rows: unknown column %r (one of %s)" % (name, sorted(MODEL_COLUMNS)))
+        lo, hi = MODEL_COLUMNS[name]
+        a = np.asarray(v, dtype=np.float32)
+        if name == "inertia":
+            if a.shape == (3, 3):
+                a = a.T.reshape(9)  # col-major
+            a = np.broadcast_to(a.reshape(-1, 9), (B, 9))
+        else:
+            a = np.broadcast_to(a.reshape(-1, 1), (B, 1))
+        rows[:, lo:hi] = a
+    return rows
+
+
 @dataclass
 class SrbdResult:
     u0: object              # (B, 12) first-step forces
@@ -141,14 +174,15 @@ def warm_len(spec):
     return {0: 0, 1: 32 * N, 2: 100 * N + 4}.get(int(spec.warm_start), -1)
 
 
-def check_inputs(spec, x0, x_ref, feet, contacts, warm=None, device=None):
+def check_inputs(spec, x0, x_ref, feet, contacts, warm=None, device=None, model=None):
     """Argument checks every SRBD entry point runs before a device pointer
     reaches the C ABI (qloco_srbd_solve_ex, qloco_mgpu_solve): a CPU tensor,
     a wrong dtype or a non-contiguous view is a ValueError here, not a GPU
     memory fault.  Shapes: x0 (B, 13), x_ref (B, 13N), feet (B, 12) or
     (B, 12N), contacts (B, 4) or (B, 4N); warm (B, warm_len(spec)) float32
-    when the spec's warm_start mode is on.  `device`: the device the tensors
-    must live on (default: x0's)."""
+    when the spec's warm_start mode is on; model (B, 16) float32 rows
+    (model_rows) when given.  `device`: the device the tensors must live on
+    (default: x0's)."""
     import torch
     B = x0.shape[0]
     N = int(spec.horizon)
@@ -176,6 +210,11 @@ def check_inputs(spec, x0, x_ref, feet, contacts, warm=None, device=None):
                 or warm.numel() != B * wl or warm.shape[0] != B):
             raise ValueError("warm: need a contiguous float32 (%d, %d) tensor on %s" % (B, wl, dev))
         named = named + (("warm", warm, torch.float32),)
+    if model is not None:
+        if (not isinstance(model, torch.Tensor) or model.dtype != torch.float32
+                or not model.is_contiguous() or model.dim() != 2 or tuple(model.shape) != (B, 16)):
+            raise ValueError("model: need a contiguous float32 (%d, 16) tensor (srbd.model_rows)" % B)
+        named = named + (("model", model, torch.float32),)
     for name, t, _ in named:
         if not t.is_cuda:
             raise ValueError("%s must be a device tensor (inputs resident in HBM)" % name)
@@ -242,11 +281,16 @@ class BatchedConvexMpc:
         return out
 
     def solve(self, x0, x_ref, feet, contacts, out=None, full=False, max_legs=None,
-              warm=None, stream=None):
+              warm=None, stream=None, model=None):
+        """model: per-robot bodies, a (B, 16) float32 device tensor of
+        model_rows() rows (qloco_srbd_solve_model), or None: the spec's body
+        for every robot.  A robot whose row is invalid (a non-finite value,
+        mass <= 0) gets status QLOCO_ERR_ARG (100) and NaN forces; the others
+        are unaffected."""
         import torch
         B = x0.shape[0]
         N = self.spec.horizon
-        check_inputs(self.spec, x0, x_ref, feet, contacts, warm=warm)
+        check_inputs(self.spec, x0, x_ref, feet, contacts, warm=warm, model=model)
         self.spec.feet_per_step = 1 if feet.shape[1] == 12 * N and N > 1 else 0
         self.spec.contacts_per_step = 1 if contacts.shape[1] == 4 * N and N > 1 else 0
         if self.spec.literal_full_qp:  # every (step, leg) pair is a variable
@@ -262,21 +306,33 @@ class BatchedConvexMpc:
         place = None
         if self.placement and self.spec.literal_full_qp and not self.spec.warm_start and B > 0:
             place = self.place_state(B, x0.device, stream)
-        check(lib().qloco_srbd_solve_placed(
-            C.byref(self.spec), B, ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts), ptr(out.u0),
-            ptr(out.u), ptr(out.status), ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
-            ptr(warm), int(max_legs), ptr(place), C.c_void_p(stream)), "qloco_srbd_solve")
+        head = (C.byref(self.spec), B, ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts), ptr(out.u0),
+                ptr(out.u), ptr(out.status), ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
+                ptr(warm), int(max_legs), ptr(place))
+        if model is None:
+            check(lib().qloco_srbd_solve_placed(*head, C.c_void_p(stream)), "qloco_srbd_solve")
+        else:
+            check(lib().qloco_srbd_solve_model(*head, ptr(model), C.c_void_p(stream)),
+                  "qloco_srbd_solve_model")
         return out
 
-    def build(self, x0, x_ref, feet, contacts=None, want=("H", "g", "lb", "ub"), stream=None):
+    def build(self, x0, x_ref, feet, contacts=None, want=("H", "g", "lb", "ub"), stream=None,
+              model=None):
         """Dense condensed-QP build only (ConvexMpc::calculate_qp_mats,
         ConvexMpc.cpp:162-264) via qloco_srbd_build.  Returns a dict of
         device tensors among H (B,12N,12N) [symmetric; stored col-major],
         g (B,12N), lb/ub (B,20N), Aqp (B,13,13N) [col-major (13N x 13)],
-        Bqp (B,12N,13N) [col-major (13N x 12N)]."""
+        Bqp (B,12N,13N) [col-major (13N x 12N)].  model: per-robot bodies as
+        for solve() (qloco_srbd_build_model)."""
         import torch
         B, N = x0.shape[0], self.spec.horizon
         dev = x0.device
+        if model is not None:
+            if (not isinstance(model, torch.Tensor) or model.dtype != torch.float32
+                    or not model.is_contiguous() or tuple(model.shape) != (B, 16)):
+                raise ValueError("model: need a contiguous float32 (%d, 16) tensor (srbd.model_rows)" % B)
+            if not model.is_cuda or model.device != dev:
+                raise ValueError("model is on %s, expected %s" % (model.device, dev))
         self.spec.feet_per_step = 1 if feet.shape[1] == 12 * N and N > 1 else 0
         if contacts is not None:
             self.spec.contacts_per_step = 1 if contacts.shape[1] == 4 * N and N > 1 else 0
@@ -285,10 +341,14 @@ class BatchedConvexMpc:
         out = {k: torch.empty(shapes[k], dtype=torch.float32, device=dev) for k in want}
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().qloco_srbd_build(
-            C.byref(self.spec), B, ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts),
-            ptr(out.get("H")), ptr(out.get("g")), ptr(out.get("lb")), ptr(out.get("ub")),
-            ptr(out.get("Aqp")), ptr(out.get("Bqp")), C.c_void_p(stream)), "qloco_srbd_build")
+        head = (C.byref(self.spec), B, ptr(x0), ptr(x_ref), ptr(feet), ptr(contacts),
+                ptr(out.get("H")), ptr(out.get("g")), ptr(out.get("lb")), ptr(out.get("ub")),
+                ptr(out.get("Aqp")), ptr(out.get("Bqp")))
+        if model is None:
+            check(lib().qloco_srbd_build(*head, C.c_void_p(stream)), "qloco_srbd_build")
+        else:
+            check(lib().qloco_srbd_build_model(*head, ptr(model), C.c_void_p(stream)),
+                  "qloco_srbd_build_model")
         return out
 
 
@@ -324,8 +384,8 @@ class PersistentConvexMpc(BatchedConvexMpc):
         self.record.zero_()
 
     def solve(self, x0, x_ref, feet, contacts, out=None, full=False, max_legs=None,
-              stream=None):
+              stream=None, model=None):
         if x0.shape[0] != self.batch:
             raise ValueError("batch %d, record holds %d controllers" % (x0.shape[0], self.batch))
         return super().solve(x0, x_ref, feet, contacts, out=out, full=full, max_legs=max_legs,
-                             warm=self.record, stream=stream)
+                             warm=self.record, stream=stream, model=model)

@@ -1,0 +1,447 @@
+"""Per-robot bodies of the SRBD MPC on the device (qloco_srbd_solve_model,
+qloco_srbd_build_model, include/qloco.h).
+
+Five bodies, instance b takes body b % 5 (values: _bodies):
+  0 the spec's Go1; 1 the reference's gazebo A1 (config/gazebo_a1_mpc.yaml:
+  12.0 kg, diag inertia 0.0158533 / 0.0377999 / 0.0456542); 2 its hardware A1
+  (13.5 kg, Ixx 0.0178533); 3 light (9 kg, 0.8 x Go1 inertia, mu 0.6, fz <= 120);
+  4 heavy (18 kg, 1.5 x Go1 inertia, mu 0.2, fz <= 250).
+
+1. A mixed batch equals the uniform calls bit for bit: row b of every output
+   of qloco_srbd_solve_model equals row b of the existing
+   qloco_srbd_solve_placed call whose spec carries body b % 5 -- a condition,
+   not a tolerance (the same kernel arithmetic on the same floats) -- for every
+   kernel family, cold, warm-started and persistent (records compared too).
+2. model = NULL is qloco_srbd_solve_placed.
+3. The rows mean what the header says: the dense build and two solves against
+   the fp64 restatement with each instance's own body, at the bounds of the
+   neighbouring tests (test_srbd_gpu.py), whose figures for these bodies are
+   in profiles/srbd_model_parity.txt.
+4. An invalid row refuses its instance and no other.
+5. The multi-GPU handle at world 1.  6. The C++ shim (tests/cpp/test_srbd_model_host.cpp).
+
+The uniform calls are computed once per case, shared and read-only."""
+import ctypes as C
+import functools
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+torch = pytest.importorskip("torch")
+
+pytestmark = pytest.mark.gpu
+
+import oracle_lib as O  # noqa: E402
+from srbd_ref import Instance, np_build  # noqa: E402
+from test_srbd_gpu import SEED, U0Bound, _dev  # noqa: E402
+
+from quadrupedal_loco_amd import _lib, srbd  # noqa: E402
+
+FIELDS = ("u0", "u", "status", "iters", "rho_updates", "obj")
+ERR_ARG = 100
+HEADER = 4  # int32 words before the placement state's hint[]
+PLACED_SIMDS = 16  # S < B = 40 <= 4 S
+
+
+def _bodies(spec):
+    """The five (mass, inertia[9] col-major, mu, fz_min, fz_max) as float32 rows."""
+    rows = srbd.model_rows(5, spec)
+    go1 = rows[0, 1:10].copy()
+    a1 = lambda ixx: np.diag([ixx, 0.0377999, 0.0456542]).T.reshape(9)
+    rows[1, :13] = [12.0, *a1(0.0158533), 0.3, 0.0, 180.0]
+    rows[2, :13] = [13.5, *a1(0.0178533), 0.3, 0.0, 180.0]
+    rows[3, :13] = [9.0, *(np.float32(0.8) * go1), 0.6, 0.0, 120.0]
+    rows[4, :13] = [18.0, *(np.float32(1.5) * go1), 0.2, 0.0, 250.0]
+    return rows
+
+
+def _spec_with(spec, row):
+    """A copy of the spec that carries the row's body."""
+    s = _lib.SrbdSpec()
+    C.memmove(C.byref(s), C.byref(spec), C.sizeof(s))
+    s.mass = float(row[0])
+    for i in range(9):
+        s.inertia[i] = float(row[1 + i])
+    s.mu, s.fz_min, s.fz_max = float(row[10]), float(row[11]), float(row[12])
+    return s
+
+
+# name -> N, gait, B, literal_full_qp, warm_start, ticks, per-step feet
+CASES = {
+    "literal one-wave": (10, "trot", 40, 1, 0, 1, False),
+    "literal one-wave, placed": (10, "trot", 40, 1, 0, 2, False),
+    "literal two-wave N=16": (16, "trot", 15, 1, 0, 1, False),
+    "literal two-wave N=13": (13, "pace", 15, 1, 0, 1, False),
+    "generic literal": (4, "trot", 20, 1, 0, 1, True),
+    "reduced one-wave": (10, "trot", 40, 0, 0, 1, False),
+    "reduced two-wave": (16, "trot", 15, 0, 0, 1, False),
+    "reduced mixed classes": (20, "mixed", 30, 0, 0, 1, False),
+    "wide": (20, "stance", 10, 0, 0, 1, False),
+    "warm_start 1, literal": (10, "trot", 40, 1, 1, 2, False),
+    "warm_start 1, reduced": (10, "trot", 40, 0, 1, 2, False),
+    "warm_start 2, literal": (10, "trot", 40, 1, 2, 3, False),
+    "warm_start 2, reduced": (10, "trot", 40, 0, 2, 3, False),
+}
+
+
+def _inputs(name):
+    """Host inputs per tick, the spec and the largest stance-leg count."""
+    N, gait, B, lit, ws, ticks, fps = CASES[name]
+    if ws:
+        seq = srbd.control_loop_sequence(SEED, N, B, ticks, gait, switch_every=2)
+    else:
+        seq = [srbd.generate(SEED, N, B, gait)] * ticks
+    if fps:  # the jitter of test_srbd_per_step_feet_reach_every_solve_kernel
+        rng = np.random.default_rng(9)
+        seq = [(x0, xr, (np.tile(ft, (1, N)) + rng.uniform(-0.02, 0.02, (B, 12 * N))).astype(np.float32), ct)
+               for x0, xr, ft, ct in seq]
+    if name == "reduced mixed classes":  # every class on purpose, one instance of each body
+        x0, xr, ft, ct = seq[0]
+        ct = ct.copy()
+        ct[0:5, 4 * 5:] = 0     # <= 20 stance legs: the one-wave class, through its list
+        ct[5:10, :] = 1         # 80: the wide kernel, as the untouched rows (43 or more)
+        ct[10:15, 4 * 10:] = 0  # 22 .. 42: the two-wave buckets
+        seq = [(x0, xr, ft, ct)]
+    spec = srbd.default_spec(horizon=N, literal_full_qp=lit, warm_start=ws)
+    spec.contacts_per_step = 1
+    spec.feet_per_step = 1 if fps else 0
+    legs = max(int(c.reshape(B, -1).sum(1).max()) for _, _, _, c in seq)
+    return seq, spec, (4 * N if lit else legs)
+
+
+def _check_family(name, seq, spec, legs):
+    """The case reaches the kernel family it is named after."""
+    N, gait, B, lit, ws, ticks, fps = CASES[name]
+    route = srbd.route(spec)
+    per = np.stack([c.reshape(B, -1).sum(1) for _, _, _, c in seq])
+    if "one-wave" in name and lit:
+        assert route == 1
+    elif "two-wave" in name and lit:
+        assert route == 2
+    elif name == "generic literal":
+        assert route == 3
+    elif lit:
+        assert route == 1  # the warm / persistent literal cases: N = 10
+    else:
+        assert route == 4
+        if name == "reduced two-wave":
+            assert ((per >= 22) & (per <= 42)).all()
+        elif name == "wide":
+            assert (per >= 43).all()
+        elif name == "reduced mixed classes":
+            assert (per <= 21).sum() >= 5 and ((per >= 22) & (per <= 42)).sum() >= 5 and (per >= 43).sum() >= 5
+        else:
+            assert (per <= 21).all()
+
+
+def _call(entry, spec, args, legs, warm=None, place=None, model=None):
+    """One raw call of qloco_srbd_solve_placed / qloco_srbd_solve_model; every
+    output array as bytes (pre-filled, so an unwritten element shows)."""
+    dev = args[0].device
+    B, N = args[0].shape[0], spec.horizon
+    out = {"u0": torch.full((B, 12), 7.0, dtype=torch.float32, device=dev),
+           "u": torch.full((B, 12 * N), 7.0, dtype=torch.float32, device=dev),
+           "status": torch.full((B,), -7, dtype=torch.int32, device=dev),
+           "iters": torch.full((B,), -7, dtype=torch.int32, device=dev),
+           "rho_updates": torch.full((B,), -7, dtype=torch.int32, device=dev),
+           "obj": torch.full((B,), 7.0, dtype=torch.float32, device=dev)}
+    p = _lib.ptr
+    head = (C.byref(spec), B, p(args[0]), p(args[1]), p(args[2]), p(args[3]), p(out["u0"]), p(out["u"]),
+            p(out["status"]), p(out["iters"]), p(out["rho_updates"]), p(out["obj"]), p(warm), int(legs), p(place))
+    st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    if entry == "placed":
+        _lib.check(_lib.lib().qloco_srbd_solve_placed(*head, st), "qloco_srbd_solve_placed")
+    else:
+        _lib.check(_lib.lib().qloco_srbd_solve_model(*head, p(model), st), "qloco_srbd_solve_model")
+    torch.cuda.synchronize()
+    res = {f: out[f].cpu().numpy() for f in FIELDS}
+    if warm is not None:
+        res["warm"] = warm.cpu().numpy()
+    return res
+
+
+def _run(name, entry, spec, model=None, placed=False):
+    """The case's ticks through one entry point: a list of per-tick results."""
+    seq, _, legs = _inputs(name)
+    dev = _dev()
+    B = seq[0][0].shape[0]
+    wl = srbd.warm_len(spec)
+    warm = torch.zeros((B, wl), dtype=torch.float32, device=dev) if wl else None
+    place = None
+    if placed:
+        place = torch.zeros(_lib.lib().qloco_srbd_place_bytes(B) // 4, dtype=torch.int32, device=dev)
+    res = []
+    for tick in seq:
+        args = tuple(torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in tick)
+        res.append(_call(entry, spec, args, legs, warm=warm, place=place, model=model))
+        if place is not None:
+            res[-1]["place"] = place.cpu().numpy()
+    return res
+
+
+@functools.lru_cache(maxsize=None)
+def _uniform(name):
+    """The five uniform calls of a case through the existing entry point
+    (read-only), with the rows of the mixed batch."""
+    seq, spec, legs = _inputs(name)
+    _check_family(name, seq, spec, legs)
+    B = seq[0][0].shape[0]
+    bodies = _bodies(spec)
+    runs = [_run(name, "placed", _spec_with(spec, bodies[k])) for k in range(5)]
+    for run in runs:
+        for tick in run:
+            for v in tick.values():
+                v.setflags(write=False)
+    rows = bodies[np.arange(B) % 5].copy()
+    rows.setflags(write=False)
+    return runs, rows
+
+
+def _rows_dev(rows):
+    return torch.from_numpy(np.array(rows, np.float32)).to(_dev())
+
+
+def _same_bytes(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8))
+
+
+def _assert_rows_equal_uniform(name, mixed, runs, skip=()):
+    B = mixed[0]["u0"].shape[0]
+    for t, tick in enumerate(mixed):
+        for f in FIELDS + (("warm",) if "warm" in tick else ()):
+            for b in range(B):
+                if b in skip:
+                    continue
+                assert _same_bytes(tick[f][b], runs[b % 5][t][f][b]), (name, "tick", t, f, "row", b)
+
+
+@pytest.mark.parametrize("name", list(CASES))
+def test_mixed_batch_equals_uniform_calls_bitwise(name):
+    runs, rows = _uniform(name)
+    _, spec, _ = _inputs(name)
+    placed = name.endswith("placed")
+    if placed:
+        spec.reserved[1] = PLACED_SIMDS
+    mixed = _run(name, "model", spec, model=_rows_dev(rows), placed=placed)
+    _assert_rows_equal_uniform(name, mixed, runs)
+    # the bodies are not interchangeable here: most rows of bodies 1..4 differ
+    # from the same row of the spec's body
+    B = rows.shape[0]
+    differ = sum(not _same_bytes(mixed[0]["u0"][b], runs[0][0]["u0"][b]) for b in range(B) if b % 5)
+    assert differ >= 0.75 * (B - B // 5), differ
+    if placed:
+        # the second call ran on a valid order of this batch that is not the identity
+        B = rows.shape[0]
+        w = mixed[0]["place"]
+        assert w[0] == B and np.array_equal(w[HEADER:HEADER + B], mixed[0]["iters"])
+        order = w[HEADER + B:]
+        assert np.array_equal(np.sort(order), np.arange(B)) and not np.array_equal(order, np.arange(B))
+
+
+@pytest.mark.parametrize("name", ["literal one-wave", "literal two-wave N=16", "reduced mixed classes"])
+def test_null_model_is_solve_placed(name):
+    runs, _ = _uniform(name)
+    _, spec, _ = _inputs(name)
+    got = _run(name, "model", _spec_with(spec, _bodies(spec)[0]), model=None)
+    for t, tick in enumerate(got):
+        for f in FIELDS:
+            assert _same_bytes(tick[f], runs[0][t][f]), (name, t, f)
+
+
+# ---- 3. the rows mean what the header says
+
+def _body_kw(row):
+    """A row as the restatement's arguments (inertia as a 3 x 3 matrix)."""
+    r = np.asarray(row, np.float64)
+    return dict(mass=r[0], inertia=r[1:10].reshape(3, 3).T, mu=r[10], fz_min=r[11], fz_max=r[12])
+
+
+@pytest.mark.parametrize("N", [3, 10])
+def test_build_model_matches_restatement(N):
+    """qloco_srbd_build_model against srbd_ref.np_build with each instance's
+    own body, at the bounds of test_srbd_gpu.py::
+    test_srbd_dense_build_matches_restatement (fp32 against fp64: H rtol 2e-5,
+    g rtol 2e-4, each with an atol of a tenth of that times the largest entry;
+    bounds equal as float32; Aqp / Bqp rtol 1e-5)."""
+    dev = _dev()
+    B = 10
+    x0, xr, ft, ct = srbd.generate(SEED, N, B, "trot")
+    solver = srbd.BatchedConvexMpc(horizon=N)
+    rows = _bodies(solver.spec)[np.arange(B) % 5]
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    args = (d(x0), d(xr), d(ft), d(ct))
+    want = ("H", "g", "lb", "ub", "Aqp", "Bqp")
+    out = solver.build(*args, want=want, model=d(rows))
+    plain = solver.build(*args, want=want)
+    torch.cuda.synchronize()
+    r = {k: v.cpu().numpy().astype(np.float64) for k, v in out.items()}
+    for b in range(B):
+        kw = _body_kw(rows[b])
+        assert kw["fz_min"] == 0.0  # np_build's lower bound
+        Hn, gn, lbn, ubn, _, Aqp, Bqp = np_build(x0[b], xr[b], ft[b], ct[b], N, mass=kw["mass"], I=kw["inertia"],
+                                                 mu=kw["mu"], fz_max=kw["fz_max"])
+        assert np.allclose(r["H"][b].T, Hn, rtol=2e-5, atol=2e-6 * np.abs(Hn).max()), b
+        assert np.allclose(r["g"][b], gn, rtol=2e-4, atol=2e-5 * np.abs(gn).max()), b
+        assert np.array_equal(r["lb"][b].astype(np.float32), lbn.astype(np.float32)), b
+        assert np.array_equal(r["ub"][b].astype(np.float32), ubn.astype(np.float32)), b
+        assert np.allclose(r["Aqp"][b].T, Aqp, rtol=1e-5, atol=1e-7), b
+        assert np.allclose(r["Bqp"][b].T, Bqp, rtol=1e-5, atol=1e-9), b
+        # body 0 is the build without rows, bit for bit; the others give another H
+        if b % 5 == 0:
+            assert all(torch.equal(out[k][b], plain[k][b]) for k in want), b
+        else:
+            assert not torch.equal(out["H"][b], plain["H"][b]), b
+
+
+def _traj_metrics(u, ref, x0, xr, ft, ct, N, kw):
+    """test_srbd_gpu._traj_metrics with the instance's own mass and inertia in B_qp."""
+    u = np.asarray(u, np.float64)
+    ref = np.asarray(ref, np.float64)
+    du = (u - ref).reshape(N, 4, 3)
+    r = np.asarray(ft, np.float64).reshape(4, 3)
+    dF = np.abs(du.sum(1)).max()
+    dM = np.abs(np.cross(np.broadcast_to(r, (N, 4, 3)), du).sum(1)).max()
+    Bqp = np_build(x0, xr, ft, ct, N, mass=kw["mass"], I=kw["inertia"])[6]
+    d = Bqp @ (u - ref)
+    q = np.tile(2.0 * np.asarray(O.Q_W), N)
+    return np.abs(u[:12] - ref[:12]).max(), dF, dM, float(np.sqrt((q * d * d).sum()))
+
+
+def literal_parity(r, rows, x0, xr, ft, ct, N, report=None):
+    """The assertions of test_srbd_gpu.py::test_srbd_literal_matches_full_restatement
+    (N <= 10 form) with Instance built from each instance's own body.  r: the
+    solve's outputs; rows[b]: instance b's body.  `report`: a list that takes
+    one line of figures per instance (profiles/srbd_model_parity.txt)."""
+    B = x0.shape[0]
+    same = near = 0
+    u0b = U0Bound()
+    for b in range(B):
+        kw = _body_kw(rows[b])
+        inst = Instance(O.srbd_spec(N=N, **kw), x0[b], xr[b], ft[b], ct[b])
+        xf, info = inst.admm_full()
+        u = r["u"][b].astype(np.float64)
+        du0, dF, dM, dX = _traj_metrics(u, xf, x0[b], xr[b], ft[b], ct[b], N, kw)
+        xe, st_e, _ = inst.exact()
+        sc = max(1.0, abs(inst.obj(xe) if st_e == 0 else inst.obj(xf)))
+        dobj = abs(inst.obj(u) - inst.obj(xf)) / sc
+        swing = np.abs(u[np.repeat(ct[b] == 0, 3)]).max(initial=0.0)
+        eq = int(r["iters"][b]) == info.iters
+        if report is not None:
+            report.append("b %d mass %.1f status %d/%d iters %d/%d du0 %.3g dF %.3g dM %.3g dX %.3g dobj %.3g "
+                          "swing %.3g" % (b, kw["mass"], r["status"][b], info.status, r["iters"][b], info.iters,
+                                          du0, dF, dM, dX, dobj, swing))
+        assert r["status"][b] == 0 and info.status == 0, (b, r["status"][b], info.status)
+        assert abs(int(r["iters"][b]) - info.iters) <= 25, (b, r["iters"][b], info.iters)
+        u0b.add(du0, eq, b)
+        if eq:
+            same += 1
+            assert dX <= 0.1, (b, dX)
+            assert dF <= 15.0 and dM <= 3.0, (b, dF, dM)
+        assert dX <= 0.3, (b, dX)
+        near += int(dF <= 1.0 and dM <= 0.1)
+        assert dobj <= 5e-3, (b, dobj)
+        assert swing <= 0.25, (b, swing)
+        assert np.array_equal(r["u0"][b], r["u"][b][:12])
+    assert same >= 0.9 * B, same
+    assert near >= 0.9 * B, near
+    u0b.check()
+
+
+def reduced_parity(r, rows, x0, xr, ft, ct, N, report=None):
+    """The assertions of test_srbd_gpu.py::test_srbd_matches_admm_restatement
+    with Instance built from each instance's own body."""
+    B = x0.shape[0]
+    iters_equal = u0_close = 0
+    for b in range(B):
+        kw = _body_kw(rows[b])
+        inst = Instance(O.srbd_spec(N=N, **kw), x0[b], xr[b], ft[b], ct[b])
+        xref, info = inst.admm_reduced()
+        u = r["u"][b].astype(np.float64)
+        du = np.abs(u[:12] - xref[:12]).max()
+        fr = inst.obj(xref)
+        dobj = abs(inst.obj(u) - fr) / max(1.0, abs(fr))
+        if report is not None:
+            report.append("b %d mass %.1f status %d/%d iters %d/%d du0 %.3g dobj %.3g" % (
+                b, kw["mass"], r["status"][b], info.status, r["iters"][b], info.iters, du, dobj))
+        assert r["status"][b] == 0 and info.status == 0, (b, r["status"][b], info.status)
+        assert abs(int(r["iters"][b]) - info.iters) <= 25, (b, r["iters"][b], info.iters)
+        iters_equal += int(r["iters"][b]) == info.iters
+        assert du <= 5.0, (b, u[:12], xref[:12])
+        u0_close += int(du <= 0.5)
+        assert dobj <= 1e-3, (b, dobj)
+        assert np.all(u[np.repeat(ct[b] == 0, 3)] == 0.0)
+        assert np.array_equal(r["u0"][b], r["u"][b][:12])
+    assert iters_equal >= 0.9 * B
+    assert u0_close >= 0.9 * B
+
+
+@pytest.mark.parametrize("name,parity", [("literal one-wave", literal_parity), ("reduced two-wave", reduced_parity)])
+def test_mixed_batch_matches_restatement_per_body(name, parity):
+    """Each instance of the mixed batch against the fp64 restatement of ITS
+    body.  The bounds are the neighbouring tests', measured there on the
+    default body; for bodies 1..4 the yardstick is the uniform call of the
+    existing entry point, which test 1 ties to this path bit for bit, and
+    profiles/srbd_model_parity.txt holds its figures under the same
+    assertions: no bound needed widening."""
+    _, rows = _uniform(name)
+    seq, spec, _ = _inputs(name)
+    mixed = _run(name, "model", spec, model=_rows_dev(rows))[0]
+    x0, xr, ft, ct = seq[0]
+    parity(mixed, rows, x0, xr, ft, ct, spec.horizon)
+
+
+# ---- 4. an invalid row
+
+@pytest.mark.parametrize("name", ["literal one-wave", "reduced one-wave"])
+def test_invalid_row_refuses_one_instance_only(name):
+    runs, rows = _uniform(name)
+    _, spec, _ = _inputs(name)
+    bad = rows.copy()
+    bad[7, 0] = 0.0          # mass = 0
+    bad[11, 1 + 4] = np.nan  # an inertia entry
+    got = _run(name, "model", spec, model=_rows_dev(bad))
+    for b in (7, 11):
+        t = got[0]
+        assert t["status"][b] == ERR_ARG and t["iters"][b] == 0 and t["rho_updates"][b] == 0, (b, t["status"][b])
+        assert np.isnan(t["u0"][b]).all() and np.isnan(t["u"][b]).all() and np.isnan(t["obj"][b]), b
+    _assert_rows_equal_uniform(name, got, runs, skip=(7, 11))
+
+
+# ---- 5. the multi-GPU handle, world 1
+
+@pytest.mark.parametrize("mode,gait", [(0, "trot"), (1, "mixed")])
+def test_handle_world1_with_rows_matches_single_gpu_solve(mode, gait):
+    """test_mgpu.py::test_handle_world1_matches_single_gpu_solve with rows."""
+    from quadrupedal_loco_amd import mgpu
+    dev = torch.device("cuda", 0)
+    torch.cuda.set_device(dev)
+    N, total = 10, 512
+    args = [torch.from_numpy(a).to(dev) for a in srbd.generate(SEED, N, total, gait)]
+    solver = srbd.BatchedConvexMpc(horizon=N)
+    rows = _rows_dev(_bodies(solver.spec)[np.arange(total) % 5])
+    ref = solver.solve(*args, model=rows)
+    plain = solver.solve(*args)
+    torch.cuda.synchronize()
+    assert not torch.equal(ref.u0, plain.u0)
+    h = mgpu.MgpuSolver(srbd.default_spec(horizon=N), total, 1, 0, mgpu.unique_id(), mode)
+    for stats in (False, True):
+        h.u0_all.fill_(float("nan"))
+        u0 = h.solve(*args, stats=stats, model=rows)
+        torch.cuda.synchronize()
+        assert torch.equal(u0, ref.u0)
+        if stats:
+            assert torch.equal(h.status_all, ref.status) and torch.equal(h.iters_all, ref.iters)
+    h.close()
+
+
+# ---- 6. the C++ shim
+
+def test_cpp_set_models():
+    from quadrupedal_loco_amd import build
+    _dev()
+    exe = build.build_srbd_model_host_test()
+    assert os.path.exists(exe)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
