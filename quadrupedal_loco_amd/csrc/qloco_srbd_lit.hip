@@ -242,46 +242,108 @@ __device__ __forceinline__ void tdot2(float v0, const Shift5 &c, float v1, const
         "v"(d.c0), "v"(d.cm1), "v"(d.cm2), "v"(d.cp1), "v"(d.cp2));
 }
 
-// In-place Gauss-Jordan inverse of the 60 x 60 SPD S (one row per lane,
-// pivots <= 1 after the 1/max-diagonal scaling): invert_w1's scheme (DESIGN.md
-// §3) with one pivot of look-ahead -- pivot k first applies its update to
-// column k + 1 alone (the same fused multiply-add the full update performs,
-// so bit-identical) and publishes pivot k + 1's broadcast row, then runs the
-// other 59 columns while that LDS write is in flight.
-__device__ __forceinline__ void lit_invert(LitLds<1> &S, int lane, int ncol, Row<1> &K) {
+// In-place Gauss-Jordan inverse of the 60 x 60 SPD S (one row per lane in and
+// out, pivots <= 1 after the 1/max-diagonal scaling): invert_w1's element
+// scheme, pivot for pivot and entry for entry, with the rank-1
+// update K[i][j] = fma(c_j, ng_i, K[i][j]) of all 64 x 64 entries on the matrix
+// cores -- two v_mfma_f32_32x32x1_2b_f32 per pivot instead of 60
+// v_fmac_f32_dpp, each entry still one fused multiply-add of the same
+// operands, so the same bits (tools/micro/lit_mfma_gj.hip).
+//
+// Accumulator layout.  The 64 x 64 matrix is four 32 x 32 blocks
+// (jb, ib) = (j / 32, i / 32) of (column j, row i); the MFMA's row index is the
+// column j and its column index, the lane, the row i.  Register q of block
+// (jb, ib) holds, in lane l, K[32 ib + (l & 31)][32 jb + j0(q) + 4 (l / 32)] with
+// j0(q) = (q & 3) + 8 (q / 4) (the 32 x 32 C/D map).  D1 carries the blocks
+// (0, 0) and (1, 1) -- operands c and ng as they stand --, D2 the blocks (0, 1)
+// and (1, 0) -- ng with its lane halves exchanged.  Row registers j0 and
+// j0 + 4 of a half jb turn into register q of the blocks (jb, 0) and (jb, 1) by
+// one v_permlane32_swap, and back by the same swap: no entry is assumed equal
+// to its transpose.  Column k of every row is then one register of each of the
+// blocks (jb, 0), (jb, 1), in lane half (k / 4) & 1: one more swap makes it the
+// 64-lane vector v, and nothing goes through LDS.
+typedef float f32x32 __attribute__((ext_vector_type(32)));
+__device__ __forceinline__ void lit_swap32(float &a, float &b) {
+  const auto r = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b), false, false);
+  // (elements copied out first: __builtin_bit_cast of the vector element r[1]
+  // itself reads element 0 with this compiler)
+  const unsigned r0 = r[0], r1 = r[1];
+  a = __builtin_bit_cast(float, r0);  // (a's lanes < 32, b's lanes < 32)
+  b = __builtin_bit_cast(float, r1);  // (a's lanes >= 32, b's lanes >= 32)
+}
+constexpr int lit_gj_j0(int q) { return (q & 3) + 8 * (q >> 2); }
+
+template <int k>
+__device__ __forceinline__ void lit_pivot(f32x32 &D1, f32x32 &D2) {
+  constexpr int jb = k >> 5, kk = k & 31, h = (kk >> 2) & 1, q = (kk & 3) + 4 * (kk >> 3);
+  static_assert(lit_gj_j0(q) + 4 * h == kk, "column k: register q of the blocks (jb, .), lane half h");
+  constexpr int x = jb == 0 ? q : 16 + q;  // block (jb, 0) is D1[x] for jb = 0, D2[x] for jb = 1; block (jb, 1) the other
+  // the pivot's lane predicates are constants of k: 64-bit lane masks in SGPRs
+  // as the select conditions
+  const bool is_k = __builtin_amdgcn_inverse_ballot_w64(1ull << k);
+  const bool before_k = __builtin_amdgcn_inverse_ballot_w64((1ull << k) - 1ull);
+  const bool lo = __builtin_amdgcn_inverse_ballot_w64(0xffffffffull);
+  float X = jb == 0 ? D1[x] : D2[x], Y = jb == 0 ? D2[x] : D1[x];
+  lit_swap32(X, Y);
+  const float v = h == 0 ? X : Y;  // lane i: K[i][k]
+  const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
+  const float pinv = __builtin_amdgcn_rcpf(p);
+  const float ng = is_k ? pinv - 1.0f : -v * pinv;  // -(1 - pinv), -(v pinv): the same bits, no sign flip after the select
+  const float c = is_k ? p + 1.0f : (before_k ? -v : v);  // row k from column k (the symmetric sweep's signs)
+  float nl = ng, nh = ng;
+  lit_swap32(nl, nh);
+  const float ngs = lo ? nh : nl;  // ng with its lane halves exchanged
+  D1 = __builtin_amdgcn_mfma_f32_32x32x1f32(c, ng, D1, 0, 0, 0);
+  D2 = __builtin_amdgcn_mfma_f32_32x32x1f32(c, ngs, D2, 0, 0, 0);
+  if (p > kGjExactPivot) {  // column k exactly: rows < 32 sit in block (jb, 0), rows >= 32 in block (jb, 1), lane half h
+    const bool is_ks = __builtin_amdgcn_inverse_ballot_w64(1ull << (k ^ 32));
+    const bool half_h = h == 0 ? lo : !lo;
+    const float e = is_k ? pinv : ng, es = is_ks ? pinv : ngs;
+    const float e0 = h == 0 ? e : es, e1 = h == 0 ? es : e;
+    if constexpr (jb == 0) {
+      D1[x] = half_h ? e0 : D1[x];
+      D2[x] = half_h ? e1 : D2[x];
+    } else {
+      D2[x] = half_h ? e0 : D2[x];
+      D1[x] = half_h ? e1 : D1[x];
+    }
+  }
+}
+
+__device__ __forceinline__ void lit_invert(int ncol, Row<1> &K) {
   int nc = __builtin_amdgcn_readfirstlane(ncol);
-  {
-    const float v = K.k[0];
-    const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 0));
-    reinterpret_cast<float *>(&S.bc[0][0][0])[lane] = lane == 0 ? p + 1.0f : v;
+  f32x32 D1, D2;
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      float a = K.k[32 * jb + lit_gj_j0(q)], b = K.k[32 * jb + lit_gj_j0(q) + 4];
+      lit_swap32(a, b);  // a: block (jb, 0), b: block (jb, 1)
+      if (jb == 0) {
+        D1[q] = a;
+        D2[q] = b;
+      } else {
+        D2[16 + q] = a;
+        D1[16 + q] = b;
+      }
+    }
   }
   ColLoop<0, 60>::run([&](auto kc) {
     constexpr int k = decltype(kc)::value;
     asm volatile("" : "+s"(nc));
     if (k >= nc) return;
-    // the pivot's lane predicates (lane == k, lane == k + 1, lane <= k) are
-    // constants of k: 64-bit lane masks in SGPRs as the select conditions, no
-    // per-pivot lane index and no vector compares
-    const bool is_k = __builtin_amdgcn_inverse_ballot_w64(1ull << k);
-    lsync();
-    const f4v r0 = S.bc[0][0][lane & 15];
-    const float v = K.k[k];
-    const float p = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), k));
-    const float pinv = __builtin_amdgcn_rcpf(p);
-    const float ng = is_k ? pinv - 1.0f : -v * pinv;  // -(1 - pinv), -(v pinv): the same bits, no sign flip after the select
-    if constexpr (k + 1 < 60) {  // unconditional (harmless past the last pivot): no branch to join
-      const bool is_k1 = __builtin_amdgcn_inverse_ballot_w64(1ull << (k + 1));
-      const bool upto_k = __builtin_amdgcn_inverse_ballot_w64((2ull << k) - 1ull);
-      const float la = fmaf(dpp_col<k + 1>(r0), ng, K.k[k + 1]);
-      const float p1 = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, la), k + 1));
-      reinterpret_cast<float *>(&S.bc[0][0][0])[lane] = is_k1 ? p1 + 1.0f : (upto_k ? -la : la);
-    }
-    // (the _P1 block opens with s_nop 1, not 4: r0 comes straight from the ds_read and this
-    // function's control flow is scalar, so no VALU write of EXEC precedes the DPP)
-    QL_DPP_GJ60_P1(K.k, 0, r0, ng);
-    if (p > kGjExactPivot) K.k[k] = is_k ? pinv : ng;
+    lit_pivot<k>(D1, D2);
   });
-  lsync();
+#pragma unroll
+  for (int jb = 0; jb < 2; ++jb) {
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+      float a = jb == 0 ? D1[q] : D2[16 + q], b = jb == 0 ? D2[q] : D1[16 + q];
+      lit_swap32(a, b);
+      K.k[32 * jb + lit_gj_j0(q)] = a;
+      K.k[32 * jb + lit_gj_j0(q) + 4] = b;
+    }
+  }
 }
 
 // The two-wave form: S is (60 + 60) x (60 + 60) in column space (wave w's
@@ -1244,7 +1306,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
         for (int c = 60 * W; c < 64 * W; ++c) T.k[c] = 0.0f;
       }
       if constexpr (W == 1)
-        lit_invert(S, lxf, nw, T);  // (sM M)^-1
+        lit_invert(nw, T);  // (sM M)^-1
       else
         lit_invert2(S, wv, 6 * H, 6 * (N - H), T);
 #pragma unroll
@@ -1253,7 +1315,7 @@ __device__ __forceinline__ void srbd_lit_one(const SrbdArgs &a, LitLds<W> &S, co
       // as leg-triple shifts (D^-1 applied elementwise around the two dots)
 #pragma unroll
       // (the rows written for U above, read back: the inversion works in
-      // S.bc and the T registers alone, so w0i still holds them)
+      // registers (two waves: and S.bc), so w0i still holds them)
       for (int h = 0; h < 2; ++h) {
         const float wx = S.w0i[wv][0][h][lxf], wy = S.w0i[wv][1][h][lxf], wz = S.w0i[wv][2][h][lxf];
         W1[h] = shift5(valid[h] ? wx : 0.0f, valid[h] ? wy : 0.0f, valid[h] ? wz : 0.0f, comp);

@@ -4,7 +4,7 @@
 Compiles quadrupedal_loco_amd/csrc/qloco_srbd_lit.hip for gfx950, device
 only, to assembly with the flags of quadrupedal_loco_amd/build.py plus line
 tables, and counts, per kernel and per phase of srbd_lit_one, the VALU
-instructions (fp64 ones apart), LDS instructions and s_nop padding.  Every
+instructions (fp64 ones and MFMA apart), LDS instructions and s_nop padding.  Every
 instruction is attributed to the source line of its line-table entry; lines
 of inlined helpers outside srbd_lit_one (DPP macros, math library code) count
 for the phase of the last srbd_lit_one line seen before them, so the split
@@ -121,10 +121,12 @@ def census(asm, src):
         if not m:
             continue
         op = m.group(1)
-        row = cur.setdefault(ph, {"valu": 0, "f64": 0, "lds": 0, "nop": 0, "vmem": 0})
+        row = cur.setdefault(ph, {"valu": 0, "f64": 0, "mfma": 0, "lds": 0, "nop": 0, "vmem": 0})
         if op.startswith("v_"):
             row["valu"] += 1
-            if re.search(r"_f64|_i64|_u64|_b64", op):
+            if op.startswith("v_mfma"):
+                row["mfma"] += 1
+            elif re.search(r"_f64|_i64|_u64|_b64", op):
                 row["f64"] += 1
         elif op.startswith("ds_"):
             row["lds"] += 1
@@ -188,23 +190,23 @@ def main():
     names, kernels, meta = census(asm, a.src)
     loops = inner_loop(asm)
     print("# literal SRBD kernels: static instruction census %s" % a.tag)
-    print("# (static counts per phase of srbd_lit_one; 64-bit VALU counted apart and included in VALU)")
+    print("# (static counts per phase of srbd_lit_one; 64-bit VALU and MFMA counted apart and included in VALU)")
     for k in sorted(kernels):
         r = meta.get(k, {})
         print("\n%s" % k)
         print("  vgpr %s  sgpr %s  lds %s B  private %s B  spills %s  kernarg %s B" % (
             r.get("vgpr_count"), r.get("sgpr_count"), r.get("group_segment_fixed_size"),
             r.get("private_segment_fixed_size"), r.get("vgpr_spill_count"), r.get("kernarg_segment_size")))
-        print("  %-34s %7s %7s %6s %6s %6s" % ("phase", "VALU", "64-bit", "LDS", "s_nop", "VMEM"))
-        tot = {"valu": 0, "f64": 0, "lds": 0, "nop": 0, "vmem": 0}
+        print("  %-34s %7s %7s %6s %6s %6s %6s" % ("phase", "VALU", "64-bit", "MFMA", "LDS", "s_nop", "VMEM"))
+        tot = {"valu": 0, "f64": 0, "mfma": 0, "lds": 0, "nop": 0, "vmem": 0}
         for n in names:
             row = kernels[k].get(n)
             if not row:
                 continue
-            print("  %-34s %7d %7d %6d %6d %6d" % (n, row["valu"], row["f64"], row["lds"], row["nop"], row["vmem"]))
+            print("  %-34s %7d %7d %6d %6d %6d %6d" % (n, row["valu"], row["f64"], row["mfma"], row["lds"], row["nop"], row["vmem"]))
             for key in tot:
                 tot[key] += row[key]
-        print("  %-34s %7d %7d %6d %6d %6d" % ("total", tot["valu"], tot["f64"], tot["lds"], tot["nop"], tot["vmem"]))
+        print("  %-34s %7d %7d %6d %6d %6d %6d" % ("total", tot["valu"], tot["f64"], tot["mfma"], tot["lds"], tot["nop"], tot["vmem"]))
         if k in loops:
             print("  ADMM inner loop, one iteration: " + ", ".join("%s %d" % kv for kv in loops[k].items()))
     if tmp:
