@@ -616,6 +616,16 @@ typedef struct qloco_a1_params {
   int32_t reserved[3];
 } qloco_a1_params;
 void qloco_a1_params_default(qloco_a1_params *p);
+/* The parameter rule.  QLOCO_OK, or QLOCO_ERR_ARG (qloco_last_error() names
+ * the field) for what OSQP v0.6's validate_settings refuses -- max_iter < 1,
+ * scaling < 0, check_termination < 0, adaptive_rho_interval < 0, rho <= 0,
+ * sigma <= 0, alpha outside (0, 2), eps_abs < 0, eps_rel < 0, both zero,
+ * adaptive_rho_tolerance < 1 -- and for a body the QP is not posed for: any
+ * non-finite double field, robot_mass <= 0, mu < 0, f_min > f_max, r < 0, a
+ * negative q_diag entry.  qloco_a1_qp_solve applies it before any device
+ * work; check_termination = 0 is legal (no termination check: the solve runs
+ * max_iter iterations and the adaptive-rho interval becomes 100). */
+int qloco_a1_params_check(const qloco_a1_params *p);
 /* Per-robot state record, double[QLOCO_A1_STATE_LEN] (A1CtrlStates fields):
  *   [0:3] root_pos  [3:6] root_pos_d  [6:9] root_euler  [9:12] root_euler_d
  *   [12:15] root_lin_vel (world)  [15:18] root_lin_vel_d (body)
@@ -624,7 +634,23 @@ void qloco_a1_params_default(qloco_a1_params *p);
  *   [42:54] foot_pos_abs (3x4 col-major, legs FL, FR, RL, RR)
  * contacts[B*4] uint8.  Outputs: forces_body[B*12] (foot_forces_grf, 3x4
  * col-major) required; qp_solution[B*12] (world frame), status[B],
- * iters[B], rho_updates[B], obj[B] optional (NULL). */
+ * iters[B], rho_updates[B], obj[B] optional (NULL); forces_body does not
+ * depend on which of them are given.  A contact flag is set when its byte is
+ * non-zero.
+ *
+ * Failed solves (per robot, status[b]; the call still returns QLOCO_OK):
+ *   QLOCO_MAX_ITER / QLOCO_SOLVED_INACCURATE  the ADMM ran max_iter iterations
+ *     without passing a termination check (iters[b] == max_iter); the status
+ *     is SOLVED_INACCURATE if the last iterate passes the check at 10 x eps
+ *     (OSQP's rule, evaluated at max_iter whether or not that is a check
+ *     iteration), else MAX_ITER.  forces_body and qp_solution hold the last
+ *     iterate, finite, as OSQP returns it.
+ *   QLOCO_NAN  the objective of the last iterate is not finite (a NaN or Inf
+ *     in the robot's state record): forces_body and qp_solution of that robot
+ *     are NaN, iters[b] is where the loop stopped.  This is the kernel's own
+ *     contract; OSQP would report a finite-looking status there.  Other robots
+ *     of the batch are not affected: their outputs are bit-identical to a
+ *     call in which that robot's record is finite. */
 #define QLOCO_A1_STATE_LEN 54
 int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, const double *state,
                       const uint8_t *contacts, double *forces_body, double *qp_solution,

@@ -292,6 +292,7 @@ struct A1QpState {
 
 class A1QpBatch {
  public:
+  // throws Error(QLOCO_ERR_ARG) for parameters qloco_a1_params_check refuses
   A1QpBatch(int batch, const qloco_a1_params *params = nullptr);
   // foot_forces_grf: B * 12 (3x4 col-major per robot)
   void compute_grf(const A1QpState *states, double *foot_forces_grf);

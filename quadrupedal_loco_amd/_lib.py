@@ -191,6 +191,7 @@ SIGNATURES = {
     "qloco_servo_force_block": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 22),
     "qloco_support_phase": (C.c_int, [i64] + [vp] * 8),
     "qloco_a1_params_default": (None, [C.POINTER(A1Params)]),
+    "qloco_a1_params_check": (C.c_int, [C.POINTER(A1Params)]),
     "qloco_a1_qp_solve": (C.c_int, [C.POINTER(A1Params), i64] + [vp] * 9),
     "qloco_a1_kin_params_default": (None, [C.POINTER(A1KinParams)]),
     "qloco_a1_leg_kin": (C.c_int, [C.POINTER(A1KinParams), i64] + [vp] * 16),

@@ -40,6 +40,14 @@ def default_params(**overrides):
     return p
 
 
+def check_params(p):
+    """The parameter rule of include/qloco.h section 9 (qloco_a1_params_check:
+    OSQP's validate_settings, finite fields, mu >= 0, f_min <= f_max, Q and R
+    non-negative); ValueError naming the field."""
+    if lib().qloco_a1_params_check(C.byref(p)) != 0:
+        raise ValueError(lib().qloco_last_error().decode())
+
+
 def _rot_zyx(roll, pitch, yaw):
     """root_rot_mat from Euler angles (Eigen AngleAxis Z * Y * X)."""
     cr, sr, cp, sp, cy, sy = (np.cos(roll), np.sin(roll), np.cos(pitch), np.sin(pitch),
@@ -113,6 +121,7 @@ class A1QpBatch:
 
     def __init__(self, params=None, **overrides):
         self.params = params if params is not None else default_params(**overrides)
+        check_params(self.params)
 
     def solve(self, state, contacts, out=None, stats=True, stream=None):
         import torch

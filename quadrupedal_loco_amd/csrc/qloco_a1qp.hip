@@ -30,6 +30,7 @@
 // (make_a1_golden.py): parity with the reference's OsqpEigen solve is
 // unpinned (OSQP is not vendored).
 #include <math.h>
+#include <stddef.h>
 #include <string.h>
 
 #include "qloco_common.hpp"
@@ -476,6 +477,41 @@ extern "C" void qloco_a1_params_default(qloco_a1_params *p) {
   p->adaptive_rho_tolerance = 5.0;
 }
 
+// The parameter rule of include/qloco.h section 9: OSQP v0.6 validate_settings
+// on the settings the kernel reads, and a body the QP is convex for.  NULL
+// if the parameters pass, else what is wrong.
+static const char *a1_params_fault(const qloco_a1_params *p) {
+  double d[offsetof(qloco_a1_params, max_iter) / sizeof(double)];  // every double field
+  memcpy(d, p, sizeof(d));
+  for (double x : d)
+    if (!isfinite(x)) return "non-finite field";
+  if (p->max_iter < 1) return "max_iter < 1";
+  if (p->scaling < 0) return "scaling < 0";
+  if (p->check_termination < 0) return "check_termination < 0";
+  if (p->adaptive_rho_interval < 0) return "adaptive_rho_interval < 0";
+  if (p->rho <= 0.0) return "rho <= 0";
+  if (p->sigma <= 0.0) return "sigma <= 0";
+  if (p->alpha <= 0.0 || p->alpha >= 2.0) return "alpha outside (0, 2)";
+  if (p->eps_abs < 0.0 || p->eps_rel < 0.0) return "negative eps_abs or eps_rel";
+  if (p->eps_abs == 0.0 && p->eps_rel == 0.0) return "eps_abs and eps_rel both zero";
+  if (p->adaptive_rho_tolerance < 1.0) return "adaptive_rho_tolerance < 1";
+  if (p->robot_mass <= 0.0) return "robot_mass <= 0";
+  if (p->mu < 0.0) return "mu < 0";
+  if (p->f_min > p->f_max) return "f_min > f_max";
+  if (p->r < 0.0) return "r < 0";
+  for (int k = 0; k < 6; ++k)
+    if (p->q_diag[k] < 0.0) return "negative q_diag entry";
+  return nullptr;
+}
+
+extern "C" int qloco_a1_params_check(const qloco_a1_params *p) {
+  if (!p) return QLOCO_ERR_ARG;
+  const char *bad = a1_params_fault(p);
+  if (!bad) return QLOCO_OK;
+  qloco::set_last_error_msg("qloco_a1_params_check", bad);
+  return QLOCO_ERR_ARG;
+}
+
 extern "C" int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, const double *state,
                                  const uint8_t *contacts, double *forces_body, double *qp_solution,
                                  int32_t *status, int32_t *iters, int32_t *rho_updates,
@@ -483,9 +519,7 @@ extern "C" int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, cons
   if (!prm || batch < 0) return QLOCO_ERR_ARG;
   if (batch == 0) return QLOCO_OK;
   if (!state || !contacts || !forces_body) return QLOCO_ERR_ARG;
-  if (prm->max_iter < 1 || prm->scaling < 0 || prm->check_termination < 0 || prm->rho <= 0.0 ||
-      prm->sigma <= 0.0 || prm->robot_mass <= 0.0)
-    return QLOCO_ERR_ARG;
+  if (qloco_a1_params_check(prm) != QLOCO_OK) return QLOCO_ERR_ARG;
   qloco::a1::Args a;
   memset(&a, 0, sizeof(a));
   a.p = *prm;

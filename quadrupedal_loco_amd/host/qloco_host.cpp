@@ -585,6 +585,7 @@ A1QpBatch::A1QpBatch(int batch, const qloco_a1_params *p)
     : batch_(positive_batch(batch, "A1QpBatch")) {
   if (p) params = *p;
   else qloco_a1_params_default(&params);
+  abi_ok(qloco_a1_params_check(&params), "A1QpBatch");  // the rule of include/qloco.h section 9
   const size_t B = batch;
   d_state_ = dalloc<double>(arena_, B * QLOCO_A1_STATE_LEN);
   d_forces_ = dalloc<double>(arena_, B * 12);

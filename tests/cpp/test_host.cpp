@@ -311,10 +311,11 @@ static void test_convex_mpc_multi_gpu() {
   std::printf("multi-GPU compute_grf ok (world 1): iters %d / %d\n", mg.iters[0], mg.iters[1]);
 }
 
-// A1RobotControl::compute_grf QP branch (A1QpBatch) vs oracle/a1_qp.c.
-static void test_a1_qp() {
+// A1RobotControl::compute_grf QP branch (A1QpBatch) vs oracle/a1_qp.c, with
+// the default parameters (gp == nullptr) or the caller's.
+static void a1_qp_against_oracle(const qloco_a1_params *gp, const char *what) {
   const int B = 8;
-  qloco::A1QpBatch qp(B);
+  qloco::A1QpBatch qp(B, gp);
   std::vector<qloco::A1QpState> st(B);
   std::mt19937_64 rng(7);
   std::uniform_real_distribution<double> U(-1.0, 1.0);
@@ -322,6 +323,31 @@ static void test_a1_qp() {
   qo_a1_params_default(&prm);
   qo_admm_settings set;
   qo_admm_settings_default(&set);
+  if (gp) {  // the body fields and the OSQP settings of qloco_a1_params, field by field
+    for (int k = 0; k < 3; ++k) {
+      prm.kp_linear[k] = gp->kp_linear[k];
+      prm.kd_linear[k] = gp->kd_linear[k];
+      prm.kp_angular[k] = gp->kp_angular[k];
+      prm.kd_angular[k] = gp->kd_angular[k];
+    }
+    for (int k = 0; k < 6; ++k) prm.q_diag[k] = gp->q_diag[k];
+    prm.robot_mass = gp->robot_mass;
+    prm.r = gp->r;
+    prm.mu = gp->mu;
+    prm.f_min = gp->f_min;
+    prm.f_max = gp->f_max;
+    set.rho = gp->rho;
+    set.sigma = gp->sigma;
+    set.alpha = gp->alpha;
+    set.eps_abs = gp->eps_abs;
+    set.eps_rel = gp->eps_rel;
+    set.max_iter = gp->max_iter;
+    set.check_termination = gp->check_termination;
+    set.scaling = gp->scaling;
+    set.adaptive_rho = gp->adaptive_rho;
+    set.adaptive_rho_interval = gp->adaptive_rho_interval;
+    set.adaptive_rho_tolerance = gp->adaptive_rho_tolerance;
+  }
   for (int b = 0; b < B; ++b) {
     qloco::A1QpState &s = st[b];
     s = qloco::A1QpState{};
@@ -364,13 +390,34 @@ static void test_a1_qp() {
     double fo[12];
     qo_admm_info info;
     qo_a1_compute_grf(&prm, &set, rec, ct, fo, nullptr, &info);
-    CHECK(qp.status[b] == info.status && qp.iters[b] == info.iters, "A1 QP robot %d status/iters",
-          b);
+    CHECK(qp.status[b] == info.status && qp.iters[b] == info.iters,
+          "A1 QP (%s) robot %d status %d/%d iters %d/%d", what, b, qp.status[b], info.status,
+          qp.iters[b], info.iters);
     for (int k = 0; k < 12; ++k)
-      CHECK(std::fabs(f[b * 12 + k] - fo[k]) < 1e-5, "A1 QP robot %d [%d] %.9f vs %.9f", b, k,
-            f[b * 12 + k], fo[k]);
+      CHECK(std::fabs(f[b * 12 + k] - fo[k]) < 1e-5, "A1 QP (%s) robot %d [%d] %.9f vs %.9f", what,
+            b, k, f[b * 12 + k], fo[k]);
   }
-  std::printf("A1 QP compute_grf ok\n");
+  std::printf("A1 QP compute_grf ok (%s): status %d, iters %d\n", what, qp.status[0], qp.iters[0]);
+}
+
+static void test_a1_qp() {
+  a1_qp_against_oracle(nullptr, "defaults");
+  // off the defaults: a lower normal-force bound, and a solve that ends at
+  // max_iter off a check iteration (QLOCO_MAX_ITER / QLOCO_SOLVED_INACCURATE)
+  qloco_a1_params p;
+  qloco_a1_params_default(&p);
+  p.f_min = 20.0;
+  p.max_iter = 110;
+  a1_qp_against_oracle(&p, "f_min 20, max_iter 110");
+  // the constructor applies the parameter rule (qloco_a1_params_check)
+  p.f_min = 200.0;  // > f_max
+  int code = QLOCO_OK;
+  try {
+    qloco::A1QpBatch bad(4, &p);
+  } catch (const qloco::Error &e) {
+    code = e.status;
+  }
+  CHECK(code == QLOCO_ERR_ARG, "A1QpBatch accepted f_min > f_max (status %d)", code);
 }
 
 // Kinematicclass: per-leg calls (servo.cpp:734-741 / :1038-1051 pattern)

@@ -324,6 +324,36 @@ def test_a1_tick_with_the_qp_solver_runs_device_resident():
     assert o.forces.shape == (B, 12)
 
 
+def test_a1_tick_forces_are_the_qp_solution_of_its_own_state():
+    """The tick's forces are what the section 9 QP returns on the record and
+    the contacts the tick itself assembled (bit for bit, against a direct
+    call), and they are the restatement's solution of that QP at the
+    tolerance of tests/test_a1qp_gpu.py."""
+    import a1qp_cases as AC
+    from quadrupedal_loco_amd import a1qp
+    dev = _dev()
+    B = 3
+    inp = a1ctrl.synth_inputs(43, B, 12)
+    qp = a1qp.A1QpBatch()
+    tk = a1ctrl.A1Tick(B, dev, solver=lambda state, contacts: qp.solve(state, contacts, stats=False).forces)
+    for t in range(12):
+        o = tk.step(**{k: _t(inp[k][t], dev) for k in TICK_KEYS if k != "foot_forces_grf"})
+    torch.cuda.synchronize()
+    direct = a1qp.A1QpBatch().solve(o.state, o.swing.contacts)
+    torch.cuda.synchronize()
+    assert o.forces.shape == (B, 12) and torch.equal(o.forces, direct.forces)
+    S, CT = o.state.cpu().numpy(), o.swing.contacts.cpu().numpy()
+    assert np.all(np.isfinite(S)) and CT.any()
+    ref = AC.oracle_run(S, CT, {})
+    tol, _ = AC.force_tolerance(ref, AC.sensitivity(S, CT, {}, ref))
+    f, it = o.forces.cpu().numpy(), direct.iters.cpu().numpy()
+    assert np.array_equal(direct.status.cpu().numpy(), ref["status"])
+    assert np.all(np.abs(it - ref["iters"]) <= 25)
+    d = np.abs(f - ref["forces"]).max(axis=1)
+    print("a1 tick forces vs restatement: iters", it, ref["iters"], "|df|", d, "tol", tol)
+    assert np.all(d <= np.where(it == ref["iters"], tol, 0.5)), (d, tol)
+
+
 def test_a1_ctrl_cpp_shim_matches_c_abi():
     _dev()
     exe = os.path.join(ROOT, "tests", "cpp", "_build", "test_a1_ctrl_host")
