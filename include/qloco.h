@@ -656,6 +656,53 @@ int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, const double *s
                       const uint8_t *contacts, double *forces_body, double *qp_solution,
                       int32_t *status, int32_t *iters, int32_t *rho_updates, double *obj,
                       void *stream);
+/* One robot's body and controller tuning: the first 23 doubles of
+ * qloco_a1_params in the same order (everything up to `rho`), plus one pad.
+ * The reference controller has one A1CtrlStates per process, so a fleet with
+ * randomised payloads, friction or gains is a row per robot here where it is a
+ * yaml per robot there.  The OSQP settings (rho .. adaptive_rho_interval) stay
+ * per batch: they steer the trip counts and the shape of the loop. */
+typedef struct qloco_a1_body {            /* 192 bytes */
+  double kp_linear[3], kd_linear[3], kp_angular[3], kd_angular[3];
+  double robot_mass;
+  double q_diag[6];
+  double r;
+  double mu;
+  double f_min, f_max;
+  double reserved;                        /* written 0 by the helpers, not read */
+} qloco_a1_body;
+/* rows[0 .. count) <- the body fields of p (host pointers, no device work).
+ * QLOCO_ERR_ARG for a NULL p, a negative count, or NULL rows with count > 0. */
+int qloco_a1_body_from_params(const qloco_a1_params *p, int64_t count, qloco_a1_body *rows);
+/* The body half of the parameter rule above, on a host row: every double
+ * finite, robot_mass > 0, mu >= 0, f_min <= f_max, r >= 0, no negative q_diag
+ * entry (`reserved` is not read).  QLOCO_OK, or QLOCO_ERR_ARG with the field
+ * named by qloco_last_error().  It is the same function qloco_a1_params_check
+ * applies to the parameters' body fields, and the one the kernel applies to
+ * every row. */
+int qloco_a1_body_check(const qloco_a1_body *row);
+/* qloco_a1_qp_solve with per-robot bodies.  body: device memory, `batch`
+ * rows, only read; or NULL, which is exactly qloco_a1_qp_solve (it forwards
+ * here).  With rows, robot b takes the 23 body quantities from body[b] and
+ * the solver settings from prm; prm's own body fields are then ignored,
+ * except that prm is still validated whole before any device work.
+ *
+ * A robot's outputs are byte-identical to those of a call without rows whose
+ * prm carries its row's values, whatever its position in the batch, its
+ * neighbours' bodies and the optional outputs given.
+ *
+ * An invalid row (one qloco_a1_body_check refuses) is found on the device and
+ * that robot is not solved: status[b] = QLOCO_ERR_ARG, forces_body,
+ * qp_solution and obj NaN, iters[b] = rho_updates[b] = 0; the call still
+ * returns QLOCO_OK and every other robot is bit-identical to a call in which
+ * that row is valid.  QLOCO_ERR_ARG wins over QLOCO_NAN where both apply.
+ *
+ * Still one value per batch: the solver settings.  The Go1 force QP
+ * (section 3) and the servo ticks (sections 7, 16) take one body per call. */
+int qloco_a1_qp_solve_body(const qloco_a1_params *prm, int64_t batch, const double *state,
+                           const uint8_t *contacts, double *forces_body, double *qp_solution,
+                           int32_t *status, int32_t *iters, int32_t *rho_updates, double *obj,
+                           const qloco_a1_body *body, void *stream);
 
 /* ====================================================================== */
 /* 10. Multi-GPU handles                         */

@@ -296,6 +296,13 @@ class A1QpBatch {
   A1QpBatch(int batch, const qloco_a1_params *params = nullptr);
   // foot_forces_grf: B * 12 (3x4 col-major per robot)
   void compute_grf(const A1QpState *states, double *foot_forces_grf);
+  // Per-robot bodies (qloco_a1_body, include/qloco.h section 9): host_rows
+  // holds B rows, in compute_grf's order, copied to the device now;
+  // compute_grf then solves robot b with its row's gains, mass, weights, mu
+  // and f_min / f_max in place of params' (the solver settings stay params').
+  // nullptr returns to params.  A robot with an invalid row gets status
+  // QLOCO_ERR_ARG and NaN forces.
+  void set_bodies(const qloco_a1_body *host_rows);
   qloco_a1_params params;
   std::vector<int32_t> status, iters;
 
@@ -303,6 +310,8 @@ class A1QpBatch {
   int batch_;
   DeviceArena arena_;
   double *d_state_, *d_forces_;
+  qloco_a1_body *d_body_ = nullptr;  // set_bodies' rows (allocated on first use)
+  bool use_body_ = false;
   uint8_t *d_ct_;
   int32_t *d_st_, *d_it_;
 };

@@ -57,6 +57,12 @@ class A1Params(C.Structure):
                 ("adaptive_rho_interval", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
+class A1Body(C.Structure):
+    """Mirror of `qloco_a1_body`: one robot's body and gains, 192 bytes (the
+    first 23 doubles of `qloco_a1_params` and one pad)."""
+    _fields_ = A1Params._fields_[:10] + [("reserved", C.c_double)]
+
+
 class A1KinParams(C.Structure):
     """Mirror of `qloco_a1_kin_params`."""
     _fields_ = [("rho_fix", (C.c_double * 5) * 4), ("rho_opt", (C.c_double * 3) * 4)]
@@ -193,6 +199,9 @@ SIGNATURES = {
     "qloco_a1_params_default": (None, [C.POINTER(A1Params)]),
     "qloco_a1_params_check": (C.c_int, [C.POINTER(A1Params)]),
     "qloco_a1_qp_solve": (C.c_int, [C.POINTER(A1Params), i64] + [vp] * 9),
+    "qloco_a1_body_from_params": (C.c_int, [C.POINTER(A1Params), i64, C.POINTER(A1Body)]),
+    "qloco_a1_body_check": (C.c_int, [C.POINTER(A1Body)]),
+    "qloco_a1_qp_solve_body": (C.c_int, [C.POINTER(A1Params), i64] + [vp] * 10),
     "qloco_a1_kin_params_default": (None, [C.POINTER(A1KinParams)]),
     "qloco_a1_leg_kin": (C.c_int, [C.POINTER(A1KinParams), i64] + [vp] * 16),
     "qloco_a1_ekf_params_default": (None, [C.POINTER(A1EkfParams)]),

@@ -196,7 +196,9 @@ class A1Tick:
     `solver(state_record, contacts)` -> joint torques.  Every call goes to the
     same stream in that order.  `solver` returns body-frame forces (B, 12),
     e.g. lambda s, c: a1qp.A1QpBatch().solve(s, c).forces; with solver=None the chain stops after the
-    terrain call and the torques use `foot_forces_grf` if given."""
+    terrain call and the torques use `foot_forces_grf` if given.  A fleet with per-robot bodies
+    passes its rows (a1qp.body_rows, on the device) through the same callable:
+    solver=lambda s, c: qp.solve(s, c, body=rows, stats=False).forces."""
 
     def __init__(self, batch, device, solver=None, use_terrain=True, kin=None, ctrl=None, est=None):
         import torch

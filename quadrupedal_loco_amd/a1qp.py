@@ -20,7 +20,7 @@ from dataclasses import dataclass
 
 import numpy as np
 
-from ._lib import A1Params, check, lib, ptr
+from ._lib import A1Body, A1Params, check, lib, ptr
 
 STATE_LEN = 54  # QLOCO_A1_STATE_LEN
 
@@ -45,6 +45,63 @@ def check_params(p):
     OSQP's validate_settings, finite fields, mu >= 0, f_min <= f_max, Q and R
     non-negative); ValueError naming the field."""
     if lib().qloco_a1_params_check(C.byref(p)) != 0:
+        raise ValueError(lib().qloco_last_error().decode())
+
+
+# qloco_a1_body as 24 doubles: field -> (first, past-the-last) column
+BODY_LEN = 24
+BODY_COLUMNS = {"kp_linear": (0, 3), "kd_linear": (3, 6), "kp_angular": (6, 9), "kd_angular": (9, 12),
+                "robot_mass": (12, 13), "q_diag": (13, 19), "r": (19, 20), "mu": (20, 21),
+                "f_min": (21, 22), "f_max": (22, 23)}
+
+
+def body_rows(batch, params=None, **columns):
+    """Per-robot bodies for A1QpBatch.solve(body=): a (B, 24) float64 host
+    array in qloco_a1_body's layout (kp_linear[3] | kd_linear[3] | kp_angular[3]
+    | kd_angular[3] | robot_mass | q_diag[6] | r | mu | f_min | f_max | one
+    reserved zero), every row filled from `params` (default: default_params())
+    by qloco_a1_body_from_params.  `columns` then overwrite whole fields by
+    name: a scalar for every entry of every robot, the field's own vector (3 or
+    6 values) for every robot, or a per-robot array, (B,) for a scalar field
+    and (B, 3) / (B, 6) for a vector one.  Edit single rows in place, then move
+    the array to the device (torch.from_numpy(rows).to(dev))."""
+    B = int(batch)
+    rows = np.zeros((B, BODY_LEN), np.float64)
+    p = params if params is not None else default_params()
+    check(lib().qloco_a1_body_from_params(C.byref(p), B, rows.ctypes.data_as(C.POINTER(A1Body))),
+          "qloco_a1_body_from_params")
+    for name, v in columns.items():
+        if name not in BODY_COLUMNS:
+            raise ValueError("body_rows: unknown field %r (one of %s)" % (name, sorted(BODY_COLUMNS)))
+        lo, hi = BODY_COLUMNS[name]
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 1 and hi - lo == 1:
+            a = a.reshape(-1, 1)          # (B,) of a scalar field
+        rows[:, lo:hi] = np.broadcast_to(a, (B, hi - lo))
+    return rows
+
+
+def body_rows_from_srbd(model_rows, params=None):
+    """Rows for a fleet described by srbd.model_rows (the A1 MPC branch's
+    per-robot bodies): robot_mass, mu, f_min and f_max from its float32 columns
+    mass, mu, fz_min and fz_max, widened exactly; gains and weights from
+    `params`.  One fleet description then serves both A1 branches."""
+    from .srbd import MODEL_COLUMNS
+    m = np.asarray(model_rows)
+    if m.ndim != 2 or m.shape[1] != 16 or m.dtype != np.float32:
+        raise ValueError("model_rows: a (B, 16) float32 array of srbd.model_rows expected")
+    col = lambda k: m[:, MODEL_COLUMNS[k][0]].astype(np.float64)
+    return body_rows(len(m), params, robot_mass=col("mass"), mu=col("mu"), f_min=col("fz_min"),
+                     f_max=col("fz_max"))
+
+
+def check_body(row):
+    """The body half of the parameter rule on one row of body_rows
+    (qloco_a1_body_check); ValueError naming the field."""
+    r = np.ascontiguousarray(row, np.float64)
+    if r.shape != (BODY_LEN,):
+        raise ValueError("row: %d doubles expected" % BODY_LEN)
+    if lib().qloco_a1_body_check(r.ctypes.data_as(C.POINTER(A1Body))) != 0:
         raise ValueError(lib().qloco_last_error().decode())
 
 
@@ -123,9 +180,20 @@ class A1QpBatch:
         self.params = params if params is not None else default_params(**overrides)
         check_params(self.params)
 
-    def solve(self, state, contacts, out=None, stats=True, stream=None):
+    def solve(self, state, contacts, out=None, stats=True, stream=None, body=None):
+        """body: per-robot rows (body_rows, moved to the state's device), a
+        contiguous float64 (B, 24) tensor; robot b then takes its gains, mass,
+        weights, mu and force limits from body[b] and the solver settings from
+        self.params, and a robot whose row qloco_a1_body_check would refuse
+        comes back with status QLOCO_ERR_ARG and NaN forces."""
         import torch
         B = state.shape[0]
+        if body is not None and (
+                not isinstance(body, torch.Tensor) or body.dtype != torch.float64
+                or not body.is_contiguous() or not body.is_cuda or body.device != state.device
+                or tuple(body.shape) != (B, BODY_LEN)):
+            raise ValueError("body: contiguous float64 (B, %d) tensor on the state's device expected"
+                             % BODY_LEN)
         if (state.dtype != torch.float64 or not state.is_contiguous() or not state.is_cuda
                 or tuple(state.shape) != (B, STATE_LEN)):
             raise ValueError("state: contiguous float64 (B, %d) device tensor expected" % STATE_LEN)
@@ -145,8 +213,14 @@ class A1QpBatch:
                 out.obj = torch.empty(B, **f64)
         if stream is None:
             stream = torch.cuda.current_stream(dev).cuda_stream
-        check(lib().qloco_a1_qp_solve(C.byref(self.params), B, ptr(state), ptr(contacts),
-                                      ptr(out.forces), ptr(out.qp_solution), ptr(out.status),
-                                      ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
-                                      C.c_void_p(stream)), "qloco_a1_qp_solve")
+        if body is None:
+            check(lib().qloco_a1_qp_solve(C.byref(self.params), B, ptr(state), ptr(contacts),
+                                          ptr(out.forces), ptr(out.qp_solution), ptr(out.status),
+                                          ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
+                                          C.c_void_p(stream)), "qloco_a1_qp_solve")
+        else:
+            check(lib().qloco_a1_qp_solve_body(C.byref(self.params), B, ptr(state), ptr(contacts),
+                                               ptr(out.forces), ptr(out.qp_solution), ptr(out.status),
+                                               ptr(out.iters), ptr(out.rho_updates), ptr(out.obj),
+                                               ptr(body), C.c_void_p(stream)), "qloco_a1_qp_solve_body")
         return out

@@ -106,6 +106,7 @@ def build(verbose=False, jobs=8):
     build_nlp_node_host_test(verbose)
     build_go1_servo_host_test(verbose)
     build_srbd_model_host_test(verbose)
+    build_a1qp_body_host_test(verbose)
     return LIB
 
 
@@ -265,6 +266,24 @@ def build_srbd_model_host_test(verbose=False):
     outdir = os.path.join(ROOT, "tests", "cpp", "_build")
     os.makedirs(outdir, exist_ok=True)
     exe = os.path.join(outdir, "test_srbd_model_host")
+    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
+        return exe
+    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
+           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
+           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return exe
+
+
+def build_a1qp_body_host_test(verbose=False):
+    """tests/cpp/test_a1qp_body_host: A1QpBatch::set_bodies against one-robot
+    objects whose params carry the row's values (no oracle link)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_a1qp_body_host.cpp")
+    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(outdir, exist_ok=True)
+    exe = os.path.join(outdir, "test_a1qp_body_host")
     if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
         return exe
     cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [

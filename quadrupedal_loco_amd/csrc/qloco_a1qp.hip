@@ -29,6 +29,7 @@
 // The fixture tests/golden/a1_qp.npz comes from the repo's own restatement
 // (make_a1_golden.py): parity with the reference's OsqpEigen solve is
 // unpinned (OSQP is not vendored).
+#include <initializer_list>
 #include <math.h>
 #include <stddef.h>
 #include <string.h>
@@ -51,7 +52,80 @@ struct Args {
   const uint8_t *contacts;
   double *forces, *x, *obj;
   int32_t *status, *iters, *rho_updates;
+  const qloco_a1_body *body;  // per-robot rows (a1_qp_kernel<true> only)
 };
+
+// qloco_a1_body is the prefix of qloco_a1_params up to rho
+constexpr int kBodyLen = 23;  // doubles of a row that are read
+static_assert(sizeof(qloco_a1_body) == 192 && offsetof(qloco_a1_body, reserved) == 184, "row layout");
+static_assert(offsetof(qloco_a1_params, rho) == kBodyLen * sizeof(double) &&
+                  offsetof(qloco_a1_params, max_iter) == 232, "params layout");
+#define QLOCO_A1_SAME_OFFSET(f) \
+  static_assert(offsetof(qloco_a1_body, f) == offsetof(qloco_a1_params, f), "row is a prefix of the params: " #f)
+QLOCO_A1_SAME_OFFSET(kp_linear);
+QLOCO_A1_SAME_OFFSET(kd_linear);
+QLOCO_A1_SAME_OFFSET(kp_angular);
+QLOCO_A1_SAME_OFFSET(kd_angular);
+QLOCO_A1_SAME_OFFSET(robot_mass);
+QLOCO_A1_SAME_OFFSET(q_diag);
+QLOCO_A1_SAME_OFFSET(r);
+QLOCO_A1_SAME_OFFSET(mu);
+QLOCO_A1_SAME_OFFSET(f_min);
+QLOCO_A1_SAME_OFFSET(f_max);
+#undef QLOCO_A1_SAME_OFFSET
+
+// The body half of the parameter rule (include/qloco.h section 9), stated once
+// for qloco_a1_params_check, qloco_a1_body_check and the kernel's rows: 0 for a
+// body the QP is posed for, 1..10 for the field (in the row's order) that holds
+// a NaN or an Inf, else 10 + the number of the broken rule (kBodyFault below).
+constexpr int kBodyFields = 10;
+template <int N>
+__host__ __device__ __forceinline__ bool finite_all(const double (&v)[N]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < N; ++k) ok = ok && isfinite(v[k]);
+  return ok;
+}
+__host__ __device__ inline int body_fault(const qloco_a1_body &r) {
+  if (!finite_all(r.kp_linear)) return 1;
+  if (!finite_all(r.kd_linear)) return 2;
+  if (!finite_all(r.kp_angular)) return 3;
+  if (!finite_all(r.kd_angular)) return 4;
+  if (!isfinite(r.robot_mass)) return 5;
+  if (!finite_all(r.q_diag)) return 6;
+  if (!isfinite(r.r)) return 7;
+  if (!isfinite(r.mu)) return 8;
+  if (!isfinite(r.f_min)) return 9;
+  if (!isfinite(r.f_max)) return 10;
+  if (r.robot_mass <= 0.0) return kBodyFields + 1;
+  if (r.mu < 0.0) return kBodyFields + 2;
+  if (r.f_min > r.f_max) return kBodyFields + 3;
+  if (r.r < 0.0) return kBodyFields + 4;
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    if (r.q_diag[k] < 0.0) return kBodyFields + 5;
+  return 0;
+}
+// the parameters' body fields as a row
+__host__ __device__ inline qloco_a1_body body_of(const qloco_a1_params &p) {
+  qloco_a1_body r;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    r.kp_linear[k] = p.kp_linear[k];
+    r.kd_linear[k] = p.kd_linear[k];
+    r.kp_angular[k] = p.kp_angular[k];
+    r.kd_angular[k] = p.kd_angular[k];
+  }
+  r.robot_mass = p.robot_mass;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) r.q_diag[k] = p.q_diag[k];
+  r.r = p.r;
+  r.mu = p.mu;
+  r.f_min = p.f_min;
+  r.f_max = p.f_max;
+  r.reserved = 0.0;
+  return r;
+}
 
 struct Slot {  // one robot's LDS
   double vec[kGroup];
@@ -87,6 +161,10 @@ __device__ __forceinline__ void gmax(Slot &S, int v, double (&val)[NV]) {
   wsync();
 }
 
+// Rows: robot b's body comes from a.body[b] (qloco_a1_qp_solve_body); without
+// them the instantiation is the kernel as it was, the body in kernel-argument
+// SGPRs.
+template <bool Rows>
 __global__ __launch_bounds__(64) void a1_qp_kernel(const Args a) {
   __shared__ __attribute__((aligned(16))) Slot slots[4];
   const int lane = threadIdx.x;
@@ -100,6 +178,32 @@ __global__ __launch_bounds__(64) void a1_qp_kernel(const Args a) {
   const int zl = 3 * leg + 2;  // the leg's z lane (slot index)
   const qloco_a1_params &P = a.p;
   const double *s = a.state + b * QLOCO_A1_STATE_LEN;
+  // The body is read in the build only.  With rows the 16 lanes of a group
+  // bring their robot's row (24 doubles, three 64-byte lines) into the slot's
+  // reduction area, which is idle until the ADMM's first gmax, and the build
+  // reads it from there where it read kernel-argument SGPRs: 23 more doubles
+  // held in VGPRs beside the state record would cost the second wave per SIMD.
+  // A row the rule refuses is replaced by prm's body, so the robot's lanes
+  // walk the same code as ever beside their three neighbours, and its outputs
+  // are overwritten at the end.
+  qloco_a1_body *const row = reinterpret_cast<qloco_a1_body *>(&S.red[0][0]);
+  static_assert(sizeof(qloco_a1_body) <= 2 * kGroup * sizeof(double), "a row fits red[0..1]");
+  bool refused = false;
+  if constexpr (Rows) {
+    const double *src = reinterpret_cast<const double *>(a.body + b);
+    S.red[0][v] = src[v];
+    if (v < 8) S.red[1][v] = src[kGroup + v];
+    wsync();
+    refused = body_fault(*row) != 0;
+    wsync();
+    if (refused && v == 0) *row = body_of(P);
+    wsync();
+  }
+  // qloco_a1_body names the fields as qloco_a1_params does: without rows Bd is P
+  const auto &Bd = [&]() -> const auto & {
+    if constexpr (Rows) return *row;
+    else return P;
+  }();
 
   // ------------------------------------------------ build (A1RobotControl.cpp:383-419)
   double acc[6];
@@ -118,15 +222,15 @@ __global__ __launch_bounds__(64) void a1_qp_kernel(const Args a) {
       wb[r] = R[3 * r + 0] * av[0] + R[3 * r + 1] * av[1] + R[3 * r + 2] * av[2];
     }
 #pragma unroll
-    for (int k = 0; k < 3; ++k) t[k] = P.kd_linear[k] * (lv_d[k] - vb[k]);
+    for (int k = 0; k < 3; ++k) t[k] = Bd.kd_linear[k] * (lv_d[k] - vb[k]);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
-      acc[r] = P.kp_linear[r] * (pos_d[r] - pos[r]);
+      acc[r] = Bd.kp_linear[r] * (pos_d[r] - pos[r]);
       acc[r] += R[r] * t[0] + R[3 + r] * t[1] + R[6 + r] * t[2];
-      acc[3 + r] = P.kp_angular[r] * ee[r];
-      acc[3 + r] += P.kd_angular[r] * (av_d[r] - wb[r]);
+      acc[3 + r] = Bd.kp_angular[r] * ee[r];
+      acc[3 + r] += Bd.kd_angular[r] * (av_d[r] - wb[r]);
     }
-    acc[2] += P.robot_mass * 9.8;
+    acc[2] += Bd.robot_mass * 9.8;
   }
   // this lane's column of inertia_inv: [e_comp; Rz^T skew(foot_leg) e_comp] (:399-405)
   double cv[6];
@@ -155,22 +259,22 @@ __global__ __launch_bounds__(64) void a1_qp_kernel(const Args a) {
 #pragma unroll
     for (int k = 0; k < 6; ++k) {
       const double cr = S.col[r][k];
-      x += (r < v) ? (cr * P.q_diag[k]) * cv[k] : (cv[k] * P.q_diag[k]) * cr;
+      x += (r < v) ? (cr * Bd.q_diag[k]) * cv[k] : (cv[k] * Bd.q_diag[k]) * cr;
     }
-    Pc[r] = valid ? x + (r == v ? P.r : 0.0) : (r == v ? 1.0 : 0.0);
+    Pc[r] = valid ? x + (r == v ? Bd.r : 0.0) : (r == v ? 1.0 : 0.0);
   }
   double q = 0.0;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) q += cv[k] * P.q_diag[k] * acc[k];
+  for (int k = 0; k < 6; ++k) q += cv[k] * Bd.q_diag[k] * acc[k];
   q = valid ? -q : 0.0;
   // constraint rows owned by this lane (ctor :28-49, contact bounds :414-419):
   //  x lane: rows [1 0 -mu], [-1 0 -mu] in (-inf, 0];  y lane: the F_y pair;
   //  z lane: [0 0 1] in [c fmin, c fmax] and an inert zero row in [0, 0]
   const bool xy = valid && comp < 2;
   double ra0 = valid ? 1.0 : 0.0, ra1 = xy ? -1.0 : 0.0;
-  double rz0 = xy ? -P.mu : 0.0, rz1 = xy ? -P.mu : 0.0;
+  double rz0 = xy ? -Bd.mu : 0.0, rz1 = xy ? -Bd.mu : 0.0;
   const double cflag = a.contacts[b * 4 + leg] ? 1.0 : 0.0;
-  double l0 = xy ? -kInf : (valid ? cflag * P.f_min : 0.0), u0 = xy ? 0.0 : (valid ? cflag * P.f_max : 0.0);
+  double l0 = xy ? -kInf : (valid ? cflag * Bd.f_min : 0.0), u0 = xy ? 0.0 : (valid ? cflag * Bd.f_max : 0.0);
   double l1 = xy ? -kInf : 0.0, u1 = 0.0;
 
   // ------------------------------------------------ modified Ruiz (OSQP scale_data; admm.c)
@@ -423,8 +527,14 @@ __global__ __launch_bounds__(64) void a1_qp_kernel(const Args a) {
 #pragma unroll
   for (int j = 0; j < kN; ++j) objv += S.vec[j];
   objv *= cinv;
-  const bool bad = !isfinite(objv);
+  bool bad = !isfinite(objv);
   if (bad) status = QLOCO_NAN;
+  if (Rows && refused) {  // the stand-in's solve is not this robot's
+    bad = true;
+    status = QLOCO_ERR_ARG;
+    iter = rho_updates = 0;
+    objv = NAN;
+  }
   if (live && valid) {
     // foot_forces_grf(:, leg) = root_rot_mat^T QPSolution.segment<3>(3 leg)
     const double *R = s + 24;
@@ -480,10 +590,19 @@ extern "C" void qloco_a1_params_default(qloco_a1_params *p) {
 // The parameter rule of include/qloco.h section 9: OSQP v0.6 validate_settings
 // on the settings the kernel reads, and a body the QP is convex for.  NULL
 // if the parameters pass, else what is wrong.
+// What a code of qloco::a1::body_fault says.
+static const char *a1_body_fault_text(int code) {
+  static const char *const kBodyFault[] = {
+      "non-finite kp_linear", "non-finite kd_linear", "non-finite kp_angular", "non-finite kd_angular",
+      "non-finite robot_mass", "non-finite q_diag", "non-finite r", "non-finite mu", "non-finite f_min",
+      "non-finite f_max", "robot_mass <= 0", "mu < 0", "f_min > f_max", "r < 0", "negative q_diag entry"};
+  return kBodyFault[code - 1];
+}
+
 static const char *a1_params_fault(const qloco_a1_params *p) {
-  double d[offsetof(qloco_a1_params, max_iter) / sizeof(double)];  // every double field
-  memcpy(d, p, sizeof(d));
-  for (double x : d)
+  const int bf = qloco::a1::body_fault(qloco::a1::body_of(*p));
+  if (bf && bf <= qloco::a1::kBodyFields) return a1_body_fault_text(bf);
+  for (double x : {p->rho, p->sigma, p->alpha, p->eps_abs, p->eps_rel, p->adaptive_rho_tolerance})
     if (!isfinite(x)) return "non-finite field";
   if (p->max_iter < 1) return "max_iter < 1";
   if (p->scaling < 0) return "scaling < 0";
@@ -495,13 +614,7 @@ static const char *a1_params_fault(const qloco_a1_params *p) {
   if (p->eps_abs < 0.0 || p->eps_rel < 0.0) return "negative eps_abs or eps_rel";
   if (p->eps_abs == 0.0 && p->eps_rel == 0.0) return "eps_abs and eps_rel both zero";
   if (p->adaptive_rho_tolerance < 1.0) return "adaptive_rho_tolerance < 1";
-  if (p->robot_mass <= 0.0) return "robot_mass <= 0";
-  if (p->mu < 0.0) return "mu < 0";
-  if (p->f_min > p->f_max) return "f_min > f_max";
-  if (p->r < 0.0) return "r < 0";
-  for (int k = 0; k < 6; ++k)
-    if (p->q_diag[k] < 0.0) return "negative q_diag entry";
-  return nullptr;
+  return bf ? a1_body_fault_text(bf) : nullptr;
 }
 
 extern "C" int qloco_a1_params_check(const qloco_a1_params *p) {
@@ -512,10 +625,34 @@ extern "C" int qloco_a1_params_check(const qloco_a1_params *p) {
   return QLOCO_ERR_ARG;
 }
 
+extern "C" int qloco_a1_body_from_params(const qloco_a1_params *p, int64_t count,
+                                         qloco_a1_body *rows) {
+  if (!p || count < 0 || (count > 0 && !rows)) return QLOCO_ERR_ARG;
+  for (int64_t b = 0; b < count; ++b) rows[b] = qloco::a1::body_of(*p);
+  return QLOCO_OK;
+}
+
+extern "C" int qloco_a1_body_check(const qloco_a1_body *row) {
+  if (!row) return QLOCO_ERR_ARG;
+  const int bf = qloco::a1::body_fault(*row);
+  if (!bf) return QLOCO_OK;
+  qloco::set_last_error_msg("qloco_a1_body_check", a1_body_fault_text(bf));
+  return QLOCO_ERR_ARG;
+}
+
 extern "C" int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, const double *state,
                                  const uint8_t *contacts, double *forces_body, double *qp_solution,
                                  int32_t *status, int32_t *iters, int32_t *rho_updates,
                                  double *obj, void *stream) {
+  return qloco_a1_qp_solve_body(prm, batch, state, contacts, forces_body, qp_solution, status, iters,
+                                rho_updates, obj, nullptr, stream);
+}
+
+extern "C" int qloco_a1_qp_solve_body(const qloco_a1_params *prm, int64_t batch,
+                                      const double *state, const uint8_t *contacts,
+                                      double *forces_body, double *qp_solution, int32_t *status,
+                                      int32_t *iters, int32_t *rho_updates, double *obj,
+                                      const qloco_a1_body *body, void *stream) {
   if (!prm || batch < 0) return QLOCO_ERR_ARG;
   if (batch == 0) return QLOCO_OK;
   if (!state || !contacts || !forces_body) return QLOCO_ERR_ARG;
@@ -532,9 +669,14 @@ extern "C" int qloco_a1_qp_solve(const qloco_a1_params *prm, int64_t batch, cons
   a.status = status;
   a.iters = iters;
   a.rho_updates = rho_updates;
+  a.body = body;
   const int64_t blocks = (batch + 3) / 4;
-  hipLaunchKernelGGL(qloco::a1::a1_qp_kernel, dim3((unsigned)blocks), dim3(64), 0,
-                     (hipStream_t)stream, a);
+  if (body)
+    hipLaunchKernelGGL(qloco::a1::a1_qp_kernel<true>, dim3((unsigned)blocks), dim3(64), 0,
+                       (hipStream_t)stream, a);
+  else
+    hipLaunchKernelGGL(qloco::a1::a1_qp_kernel<false>, dim3((unsigned)blocks), dim3(64), 0,
+                       (hipStream_t)stream, a);
   QLOCO_HIP_CHECK(hipGetLastError(), "a1_qp_kernel launch");
   return QLOCO_OK;
 }

@@ -596,6 +596,14 @@ A1QpBatch::A1QpBatch(int batch, const qloco_a1_params *p)
   iters.assign(B, 0);
 }
 
+void A1QpBatch::set_bodies(const qloco_a1_body *host_rows) {
+  use_body_ = host_rows != nullptr;
+  if (!host_rows) return;
+  if (!d_body_) d_body_ = dalloc<qloco_a1_body>(arena_, (size_t)batch_);
+  arena_.upload(d_body_, host_rows, sizeof(qloco_a1_body) * (size_t)batch_);
+  arena_.sync();  // the caller's rows may go away after the call
+}
+
 void A1QpBatch::compute_grf(const A1QpState *s, double *forces) {
   const size_t B = batch_;
   std::vector<double> st(B * QLOCO_A1_STATE_LEN);
@@ -616,9 +624,9 @@ void A1QpBatch::compute_grf(const A1QpState *s, double *forces) {
   }
   arena_.upload(d_state_, st.data(), sizeof(double) * st.size());
   arena_.upload(d_ct_, ct.data(), ct.size());
-  abi_ok(qloco_a1_qp_solve(&params, batch_, d_state_, d_ct_, d_forces_, nullptr, d_st_, d_it_,
-                           nullptr, nullptr, arena_.stream()),
-         "qloco_a1_qp_solve");
+  abi_ok(qloco_a1_qp_solve_body(&params, batch_, d_state_, d_ct_, d_forces_, nullptr, d_st_, d_it_,
+                                nullptr, nullptr, use_body_ ? d_body_ : nullptr, arena_.stream()),
+         "qloco_a1_qp_solve_body");
   arena_.download(forces, d_forces_, sizeof(double) * B * 12);
   arena_.download(status.data(), d_st_, sizeof(int32_t) * B);
   arena_.download(iters.data(), d_it_, sizeof(int32_t) * B);
