@@ -366,7 +366,9 @@ void qloco_gi_limits(int32_t *n, int32_t *p, int32_t *m);
 /*    called at servo.cpp:1224-1228 and torque_mode.cpp:1364-1367)          */
 /* ====================================================================== */
 typedef struct qloco_force_params {
-  double mass;    /* 12    dynmics_compute.cpp:31 */
+  double mass;    /* 12    dynmics_compute.cpp:31.  Stored and, as in Dynamiccclass, read by
+                   * no kernel: without body rows F_sum is built with gait::mass = 12
+                   * whatever stands here; a qloco_force_body row carries it into F_sum */
   double alpha;   /* 1e4   :61 */
   double beta;    /* 1e3   :62 */
   double gamma;   /* 10    :63 */
@@ -374,6 +376,29 @@ typedef struct qloco_force_params {
   double mu;      /* 0.25 sim (:65), 0.5 HW copy */
 } qloco_force_params;
 void qloco_force_params_default(qloco_force_params *p);
+
+/* One robot's body for the Go1 force QP, the servo force block (section 7) and
+ * the servo tick (section 16): the six qloco_force_params in the same order,
+ * then the centroidal inertia Momentum_sum of servo.cpp:375-377.  The reference
+ * has one Dynamiccclass and one gait::mass per process, so a fleet with
+ * randomised payload, friction, force limits or gains is a row per robot here. */
+typedef struct qloco_force_body {   /* 128 bytes */
+  double mass, alpha, beta, gamma, fz_max, mu;
+  double momentum[9];   /* Momentum_sum, row-major */
+  double reserved[1];   /* zero */
+} qloco_force_body;
+/* rows[0 .. count) <- p's six fields and the reference's Momentum_sum (the same
+ * nine expressions the kernels' constant is initialised with).  Host pointers,
+ * no device work.  QLOCO_ERR_ARG for a NULL p, a negative count, or NULL rows
+ * with count > 0. */
+int qloco_force_body_from_params(const qloco_force_params *p, int64_t count,
+                                 qloco_force_body *rows);
+/* The row rule, on a host row: every field finite, mass > 0, alpha, beta,
+ * gamma >= 0, fz_max >= 0, mu >= 0, reserved == 0.  alpha = beta = gamma = 0
+ * passes (it solves to QLOCO_NOT_PD as it does per call).  QLOCO_OK or
+ * QLOCO_ERR_ARG.  The kernels apply the same function to every row.  The
+ * per-call qloco_force_params are not checked. */
+int qloco_force_body_check(const qloco_force_body *row);
 
 /* Per-instance inputs (device, double):
  *   com_des[B*3], leg_des[B*12], F_force_des[B*6], rfoot_des[B*3],
@@ -425,6 +450,35 @@ int qloco_force_qp_solve_ordered(const qloco_force_params *prm, int64_t batch,
                                  const double *y_coef, double *F_leg_ref, double *grf_opt,
                                  double *F_leg_guess, int32_t *qp_solution, int32_t *status,
                                  int32_t *iters, int32_t *order_ws, void *stream);
+
+/* qloco_force_qp_solve_ordered with per-robot bodies.  body: device memory,
+ * `batch` rows, only read (`list` indexes them like every per-robot array); or
+ * NULL, which is exactly qloco_force_qp_solve_ordered (it and
+ * qloco_force_qp_solve forward here).  order_ws may be NULL as there.  With
+ * rows, robot b builds G and g0 with body[b]'s alpha, beta, gamma and CI / ci0
+ * with its mu, fz_max; mass and momentum are checked and not read; prm's
+ * fields are then used only as the stand-in below.  A robot's outputs are
+ * byte-identical to a call without rows whose prm carries its row's values,
+ * whatever its position, group width, grouping or neighbours.
+ *
+ * A row qloco_force_body_check refuses is found on the device and refuses that
+ * robot alone: status[b] = QLOCO_ERR_ARG, qp_solution[b] = 0, iters[b] = 0,
+ * F_leg_guess NaN; F_leg_ref, grf_opt and the robot's iteration count in
+ * order_ws keep their values bit for bit, so a robot whose row is corrected
+ * continues from where it stood.  Its lanes run the solve with prm as a
+ * stand-in, so its wavefront neighbours are byte-identical.  The call still
+ * returns QLOCO_OK.  No allocation inside; capturable in a HIP graph (a linear
+ * chain of nodes). */
+int qloco_force_qp_solve_body(const qloco_force_params *prm, int64_t batch,
+                              const double *com_des, const double *leg_des,
+                              const double *F_force_des, const double *rfoot_des,
+                              const double *lfoot_des, const double *base_p,
+                              const double *feet_p, const double *FT_total_des,
+                              const int32_t *mode, const int32_t *right_support,
+                              const double *y_coef, double *F_leg_ref, double *grf_opt,
+                              double *F_leg_guess, int32_t *qp_solution, int32_t *status,
+                              int32_t *iters, int32_t *order_ws,
+                              const qloco_force_body *body, void *stream);
 
 /* The hardware servo's Dynamiccclass constants (unitree_legged_real copy of
  * dynmics_compute.cpp:31,65: mass = gait::mass = 14, robot_const_para_config
@@ -576,6 +630,27 @@ int qloco_servo_force_block(const qloco_force_params *prm, int64_t batch, void *
                             const double *v_est_rel, double *F_sum, double *Force_L_R,
                             double *grf_opt, double *tau, int32_t *swing,
                             int32_t *qp_solution, int32_t *status, void *stream);
+/* The force block with per-robot bodies (section 3's qloco_force_body; device,
+ * `batch` rows, or NULL = qloco_servo_force_block, which forwards here).  With
+ * rows, F_sum of robot b is mass*ca[0], mass*ca[1], mass*g + mass*ca[2],
+ * momentum . ca with its row's mass and momentum, in the operation order of
+ * the call without rows (a row holding 12 and Momentum_sum is byte-identical
+ * to NULL), and the force QP takes the row as qloco_force_qp_solve_body does.
+ * A refused row: the glue computes F_sum with the constants as a stand-in,
+ * the QP refuses the robot (status QLOCO_ERR_ARG, qp_solution 0; F_leg_ref and
+ * grf_opt in the workspace unchanged, nothing non-finite enters the
+ * workspace), and the caller's tau and grf_opt rows of that robot are NaN. */
+int qloco_servo_force_block_body(const qloco_force_params *prm, int64_t batch, void *workspace,
+                                 const double *coma_des, const double *com_des,
+                                 const double *rfoot_des, const double *lfoot_des,
+                                 const double *body_p_des, const double *foot_des,
+                                 const int32_t *right_support, const int32_t *gait_mode,
+                                 const double *y_offset, const int32_t *loop_count,
+                                 const double *Jaco, const double *foot_rel_mea,
+                                 const double *v_est_rel, double *F_sum, double *Force_L_R,
+                                 double *grf_opt, double *tau, int32_t *swing,
+                                 int32_t *qp_solution, int32_t *status,
+                                 const qloco_force_body *body, void *stream);
 
 /* ====================================================================== */
 /* 8. slow planner's contact-phase flag, batched     */
@@ -698,7 +773,7 @@ int qloco_a1_body_check(const qloco_a1_body *row);
  * that row is valid.  QLOCO_ERR_ARG wins over QLOCO_NAN where both apply.
  *
  * Still one value per batch: the solver settings.  The Go1 force QP
- * (section 3) and the servo ticks (sections 7, 16) take one body per call. */
+ * (section 3) and the servo ticks (sections 7, 16) take qloco_force_body rows. */
 int qloco_a1_qp_solve_body(const qloco_a1_params *prm, int64_t batch, const double *state,
                            const uint8_t *contacts, double *forces_body, double *qp_solution,
                            int32_t *status, int32_t *iters, int32_t *rho_updates, double *obj,
@@ -1201,6 +1276,18 @@ int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t batch, void 
                          const double *gait_msg, const int32_t *gait_mode, const double *y_offset,
                          double *q_cmd, double *ctrl_msg, double *tau, double *grf_opt,
                          const qloco_go1_servo_diag *diag, double *gait_data, void *stream);
+/* The tick with per-robot bodies (section 3's qloco_force_body; device, `batch`
+ * rows, or NULL = qloco_go1_servo_tick, which forwards here).  Only the gait
+ * branch reads the rows, with the meaning and the refused-row rule of
+ * qloco_servo_force_block_body (the caller's tau and grf_opt rows of a refused
+ * robot are NaN; the workspace stays finite).  While the batch stands up no QP
+ * is launched, the rows are not read and nothing is refused. */
+int qloco_go1_servo_tick_body(const qloco_go1_servo_params *prm, int64_t batch, void *workspace,
+                              int64_t n_count, const double *q_mea, const double *quat,
+                              const double *gait_msg, const int32_t *gait_mode,
+                              const double *y_offset, double *q_cmd, double *ctrl_msg, double *tau,
+                              double *grf_opt, const qloco_go1_servo_diag *diag, double *gait_data,
+                              const qloco_force_body *body, void *stream);
 /* Dense state[B * QLOCO_GO1_SERVO_STATE] out of / into the workspace. */
 int qloco_go1_servo_get_state(int64_t batch, const void *workspace, double *state, void *stream);
 int qloco_go1_servo_set_state(int64_t batch, void *workspace, const double *state, void *stream);

@@ -143,6 +143,12 @@ class Dynamiccclass {
                  const double RR_p[3], const double RL_p[3], const double FT_total_des[6],
                  int mode, int right_support, double y_coefficient, int robot = 0);
   void run();
+  // Per-robot bodies (qloco_force_body, include/qloco.h section 3): host_rows
+  // holds B rows, copied to the device now (the device rows are allocated on
+  // first use); run() then solves robot b with
+  // its row's alpha, beta, gamma, fz_max and mu.  nullptr returns to params.  A robot
+  // with a refused row gets status QLOCO_ERR_ARG and keeps its members.
+  void set_bodies(const qloco_force_body *host_rows);
   // compute_joint_torques for all legs of all robots (dynmics_compute.cpp:109-138)
   void compute_joint_torques(const double *Jaco /*B*4*9*/, const int32_t *swing /*B*4*/,
                              const double *p_des, const double *p_est, const double *pv_des,
@@ -164,6 +170,8 @@ class Dynamiccclass {
       *d_grf_, *d_guess_;
   int32_t *d_mode_, *d_rs_, *d_qps_, *d_st_, *d_it_;
   int32_t *d_ord_;           // grouped-launch workspace (qloco_force_order_ws_len)
+  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
+  bool use_body_ = false;
   double *d_jt_ = nullptr;   // joint-torque staging (allocated on first use)
   int32_t *d_sw_ = nullptr;
 };
@@ -640,6 +648,12 @@ class ServoForceBlock {
             const int32_t *right_support, const int32_t *gait_mode, const double *y_offset,
             const int32_t *count_in_rt_loop, const double *Jaco, const double *foot_rel_mea,
             const double *v_est_rel);
+  // Per-robot bodies (qloco_force_body, include/qloco.h section 3): host_rows
+  // holds B rows, copied to the device now (the device rows are allocated on
+  // first use); step() then builds F_sum with
+  // robot b's mass and momentum and solves with its row.  nullptr returns to params.  A robot
+  // with a refused row gets status QLOCO_ERR_ARG and NaN grf_opt / Legs_torque.
+  void set_bodies(const qloco_force_body *host_rows);
   std::vector<double> F_sum, Force_L_R, grf_opt, Legs_torque;  // 6, 6, 12, 12 per robot
   std::vector<int32_t> swing, qp_solution, status;             // 4, 1, 1 per robot
   int batch() const { return batch_; }
@@ -651,6 +665,8 @@ class ServoForceBlock {
   void *d_ws_;
   double *d_in_, *d_out_;
   int32_t *d_iin_, *d_iout_;
+  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
+  bool use_body_ = false;
 };
 
 // ------------------------------------------------------------------------
@@ -667,6 +683,12 @@ class Go1ServoBatch {
   // (the latest /MPC/Gait row), gait_mode[B], y_offset[B]
   void tick(const double *q_mea, const double *quat, const double *slow_mpc_gait,
             const int32_t *gait_mode, const double *y_offset);
+  // Per-robot bodies (qloco_force_body, include/qloco.h section 3): host_rows
+  // holds B rows, copied to the device now (the device rows are allocated on
+  // first use); the gait branch of tick() then
+  // builds F_sum with robot b's mass and momentum and solves with its row.  nullptr returns to params.  A robot
+  // with a refused row gets status QLOCO_ERR_ARG and NaN grf_opt / Legs_torque.
+  void set_bodies(const qloco_force_body *host_rows);
   std::vector<double> q_cmd;           // lowCmd.motorCmd[j].q, B*12
   std::vector<double> state_to_MPC;    // the /control2rtmpc/state row published at :762, B*25
   std::vector<double> state_feedback;  // the member after the tick ([0] = t_int), B*25
@@ -686,6 +708,8 @@ class Go1ServoBatch {
   void *d_ws_;
   double *d_in_, *d_out_, *d_rec_;
   int32_t *d_mode_;
+  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
+  bool use_body_ = false;
 };
 
 }  // namespace qloco

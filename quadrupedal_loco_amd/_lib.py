@@ -43,6 +43,13 @@ class ForceParams(C.Structure):
     _fields_ = [(k, C.c_double) for k in ("mass", "alpha", "beta", "gamma", "fz_max", "mu")]
 
 
+class ForceBody(C.Structure):
+    """Mirror of `qloco_force_body`: one robot's body for the Go1 force QP and
+    the servo ticks, 128 bytes (the six `qloco_force_params`, Momentum_sum
+    row-major, one reserved zero)."""
+    _fields_ = ForceParams._fields_ + [("momentum", C.c_double * 9), ("reserved", C.c_double * 1)]
+
+
 class A1Params(C.Structure):
     """Mirror of `qloco_a1_params`."""
     _fields_ = [("kp_linear", C.c_double * 3), ("kd_linear", C.c_double * 3),
@@ -180,6 +187,9 @@ SIGNATURES = {
     "qloco_force_qp_solve": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 18),
     "qloco_force_qp_solve_ordered": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 19),
     "qloco_force_order_ws_len": (i64, [i64]),
+    "qloco_force_body_from_params": (C.c_int, [C.POINTER(ForceParams), i64, C.POINTER(ForceBody)]),
+    "qloco_force_body_check": (C.c_int, [C.POINTER(ForceBody)]),
+    "qloco_force_qp_solve_body": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 20),
     "qloco_leg_fk": (C.c_int, [i64] + [vp] * 7),
     "qloco_leg_ik": (C.c_int, [i64] + [vp] * 10),
     "qloco_joint_torques": (C.c_int, [i64] + [vp] * 9),
@@ -195,6 +205,7 @@ SIGNATURES = {
     "qloco_servo_workspace_bytes": (C.c_int64, [i64]),
     "qloco_servo_init": (C.c_int, [i64, vp, vp]),
     "qloco_servo_force_block": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 22),
+    "qloco_servo_force_block_body": (C.c_int, [C.POINTER(ForceParams), i64] + [vp] * 23),
     "qloco_support_phase": (C.c_int, [i64] + [vp] * 8),
     "qloco_a1_params_default": (None, [C.POINTER(A1Params)]),
     "qloco_a1_params_check": (C.c_int, [C.POINTER(A1Params)]),
@@ -246,6 +257,8 @@ SIGNATURES = {
     "qloco_go1_servo_init": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, vp]),
     "qloco_go1_servo_tick": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, i64] + [vp] * 9 +
                              [C.POINTER(Go1ServoDiag), vp, vp]),
+    "qloco_go1_servo_tick_body": (C.c_int, [C.POINTER(Go1ServoParams), i64, vp, i64] + [vp] * 9 +
+                                  [C.POINTER(Go1ServoDiag), vp, vp, vp]),
     "qloco_go1_servo_get_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_go1_servo_set_state": (C.c_int, [i64, vp, vp, vp]),
     "qloco_mgpu_shard": (C.c_int, [i64, i32, i32, i32, vp, vp, vp]),

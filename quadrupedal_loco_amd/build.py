@@ -107,6 +107,7 @@ def build(verbose=False, jobs=8):
     build_go1_servo_host_test(verbose)
     build_srbd_model_host_test(verbose)
     build_a1qp_body_host_test(verbose)
+    build_force_body_host_test(verbose)
     return LIB
 
 
@@ -284,6 +285,25 @@ def build_a1qp_body_host_test(verbose=False):
     outdir = os.path.join(ROOT, "tests", "cpp", "_build")
     os.makedirs(outdir, exist_ok=True)
     exe = os.path.join(outdir, "test_a1qp_body_host")
+    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
+        return exe
+    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
+           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
+           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return exe
+
+
+def build_force_body_host_test(verbose=False):
+    """tests/cpp/test_force_body_host: set_bodies of Dynamiccclass,
+    ServoForceBlock and Go1ServoBatch against one-robot objects (no oracle
+    link)."""
+    src = os.path.join(ROOT, "tests", "cpp", "test_force_body_host.cpp")
+    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(outdir, exist_ok=True)
+    exe = os.path.join(outdir, "test_force_body_host")
     if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
         return exe
     cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [

@@ -1,6 +1,7 @@
 // qloco_common.hpp -- shared device helpers for the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <stddef.h>
 #include <stdint.h>
 
 #include "qloco.h"
@@ -45,6 +46,33 @@ __device__ __forceinline__ float limit_scaling(float d) {
   d = d < 1e-4f ? 1.0f : d;
   return d > 1e4f ? 1e4f : d;
 }
+
+// The qloco_force_body row rule (include/qloco.h section 3), stated once for
+// qloco_force_body_check and the kernels of qloco_force.hip, qloco_servo.hip
+// and qloco_go1_servo.hip.  r: the row's 16 doubles.
+__host__ __device__ __forceinline__ bool force_body_ok(const double *r) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) ok = ok && isfinite(r[k]);
+  ok = ok && r[0] > 0.0;  // mass
+#pragma unroll
+  for (int k = 1; k < 6; ++k) ok = ok && r[k] >= 0.0;  // alpha, beta, gamma, fz_max, mu
+  return ok && r[15] == 0.0;  // reserved
+}
+static_assert(sizeof(qloco_force_body) == 128 && offsetof(qloco_force_body, momentum) == 48,
+              "force_body_ok reads the row as 16 doubles");
+
+// Momentum_sum, servo.cpp:375-377 (row-major): the constant of the two servo
+// files and what qloco_force_body_from_params writes
+#define QLOCO_MOMENTUM_SUM                                                                  \
+  {2 * 0.0168352186, 2 * 0.0004636141, 2 * 0.0002367952, 2 * 0.0004636141, 2 * 0.0656071082, \
+   2 * 3.6671e-05,   2 * 0.0002367952, 2 * 3.6671e-05,   2 * 0.0742720659}
+
+// After the output copies of the force block and the servo tick: the caller's
+// tau and grf_opt rows of every robot whose row is refused become NaN
+// (qloco_force.hip).  rows != NULL.
+int force_body_mark_refused(int64_t batch, const qloco_force_body *rows, double *tau,
+                            double *grf_opt, hipStream_t stream);
 
 }  // namespace qloco
 

@@ -141,6 +141,27 @@ struct ForceCi {
   }
   __device__ __forceinline__ double b(int c) const { return (c < 8 && (c & 1)) ? fz_max : 0.0; }
 };
+// The same rows with mu and fz_max of the group's robot read from its LDS slot
+// (ForceBodyLds below) where they are used: per-robot values are group-uniform,
+// not wave-uniform, so they cannot sit in SGPRs as the kernel arguments do, and
+// four more VGPRs held across the solve do not fit the two-wave budget.
+struct ForceCiRow {
+  const double *q;  // the slot: alpha, beta, gamma, fz_max, mu
+  __device__ __forceinline__ double a(int v, int c, int) const {
+    const int grp = c >> 3, i = (c & 7) >> 1, lo = (c & 1) == 0;
+    if (v == 3 * i + 2) return grp == 0 ? (lo ? 1.0 : -1.0) : q[4];
+    if (grp > 0 && v == 3 * i + grp - 1) return lo ? 1.0 : -1.0;
+    return 0.0;
+  }
+  __device__ __forceinline__ double b(int c) const { return (c < 8 && (c & 1)) ? q[3] : 0.0; }
+};
+// Per-robot bodies (qloco_force_qp_solve_body): the five doubles the QP reads
+// of its robot's row, 40 B per group beside ForceLds: 20,096 B per 8-robot
+// block (eight blocks per CU: 160,768 of 163,840 B), 10,048 B per 4-robot block.
+template <int FG>
+struct ForceBodyLds {
+  double q[FG][5];
+};
 
 __device__ __forceinline__ double sq(double v) { return v * v; }
 
@@ -231,115 +252,41 @@ __device__ __forceinline__ void force_distribution(const double *com_des, const 
 // launch against 58 MB of algorithmic traffic (profiles/r3ft_traffic_force_
 // qp_b65536_wpe3.json) -- so the spill-free budget is the shipped one.
 constexpr int kForceWpe = 2;
+// force_qp_kernel takes the body from the kernel arguments, force_qp_body_kernel
+// (qloco_force_qp_solve_body) one qloco_force_body row per robot.  Their
+// statements are qloco_force_qp.inc, included once per kernel under `Rows`; why
+// text and not a shared __forceinline__ function is said there.
 template <int GW>
 __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kForceWpe))) void force_qp_kernel(
     const ForceArgs a) {
-  constexpr int FG = 64 / GW, VL = (12 + GW - 1) / GW;
-  __shared__ ForceLds<FG> S;
-  const int lane = threadIdx.x, grp = lane / GW, li = lane % GW;
-  const int64_t pos = (int64_t)blockIdx.x * FG + grp;
-  if (pos >= a.batch) return;
-  const int64_t inst = a.list ? a.list[pos] : pos;
-  typename ForceLds<FG>::Grp &P = S.g[grp];
-  double *const PA = P.gi.R;  // A, 6x12 col-major (dead before the solver clears R)
-  double *const PG = P.gi.J;  // G, 12x12 col-major (read once, before J is formed)
-  static_assert(sizeof(P.gi.R) >= 72 * sizeof(double), "A fits the packed R");
-  double *const Pg0 = P.gi.z;  // g0 (dead before z is first written)
+  constexpr bool Rows = false;
+  constexpr const qloco_force_body *rows = nullptr;
+#include "qloco_force_qp.inc"
+}
+template <int GW>
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(kForceWpe))) void force_qp_body_kernel(
+    const ForceArgs a, const qloco_force_body *rows) {
+  constexpr bool Rows = true;
+#include "qloco_force_qp.inc"
+}
 
-  // ---- force_distribution (state F_leg_ref in/out) -> F_leg_guess
-  double Fref[12];
-  for (int k = 0; k < 12; ++k) Fref[k] = a.F_leg_ref[inst * 12 + k];
-  force_distribution(a.com_des + inst * 3, a.leg_des + inst * 12, a.F_force_des + inst * 6,
-                     a.mode[inst], a.y_coef[inst], a.rfoot_des + inst * 3, a.lfoot_des + inst * 3,
-                     Fref);
-  // this lane's entries by a static select chain: indexing Fref by li would put
-  // the array in scratch (a per-lane spill of 96 B, written back to HBM)
-  double guess[VL];  // F_leg_guess entries li + GW v (only their lane reads them)
-#pragma unroll
-  for (int v = 0; v < VL; ++v) {
-    guess[v] = Fref[0];
-#pragma unroll
-    for (int k = 1; k < 12; ++k) guess[v] = (li + GW * v == k) ? Fref[k] : guess[v];
-  }
-  // ---- force_opt: A (6x12, col-major) with the skew_hat quirk (:274-298)
-#pragma unroll
-  for (int v = 0; v < VL; ++v) {
-    const int r = li + GW * v;
-    if (r < 12)
-      for (int k = 0; k < 6; ++k) PA[r * 6 + k] = 0.0;
-  }
-  GI_SYNC();
-  if (li < 4) {
-    const int leg = li;
-    const double *bp = a.base_p + inst * 3;
-    const double *fp = a.feet_p + inst * 12 + 3 * leg;
-    const double v0 = bp[0] - fp[0];  // skew_hat uses vec_w[0] everywhere (comma operator)
-    for (int k = 0; k < 3; ++k) PA[(3 * leg + k) * 6 + k] = 1.0;
-    // W rows [0,-a,a],[a,0,-a],[-a,a,0]
-    const double W[3][3] = {{0.0, -v0, v0}, {v0, 0.0, -v0}, {-v0, v0, 0.0}};
-    for (int r = 0; r < 3; ++r)
-      for (int k = 0; k < 3; ++k) PA[(3 * leg + k) * 6 + 3 + r] = W[r][k];
-  }
-  GI_SYNC();
-  // G = 2 (alpha A'A + (beta+gamma) I), then (G' + G)/2 ; g0 (:300-305).
-  // A'A(r,c) and A'A(c,r) are the same products summed in the same order, so G
-  // is exactly symmetric and (G' + G)/2 = (x + x)/2 = x bit for bit: the
-  // symmetrisation is the identity and is not executed.
-#pragma unroll
-  for (int v = 0; v < VL; ++v) {
-    const int r = li + GW * v;
-    if (r < 12) {
-      for (int c = 0; c < 12; ++c) {
-        double ata = 0.0;
-        for (int k = 0; k < 6; ++k) ata += PA[r * 6 + k] * PA[c * 6 + k];
-        PG[c * 12 + r] = 2.0 * (a.alpha * ata + (r == c ? (a.beta + a.gamma) : 0.0));
-      }
-    }
-  }
-  GI_SYNC();
-#pragma unroll
-  for (int v = 0; v < VL; ++v) {
-    const int r = li + GW * v;
-    if (r < 12) {
-      double atf = 0.0;
-      const double *FT = a.FT_total_des + inst * 6;
-      for (int k = 0; k < 6; ++k) atf += PA[r * 6 + k] * FT[k];
-      const double prev = a.grf_opt[inst * 12 + r];
-      Pg0[r] = -2.0 * (a.alpha * atf + a.beta * guess[v] + a.gamma * prev);
-      // _X = grf_opt (:391).  A failed Cholesky leaves the solver before it
-      // forms x (EiQuadProg.cpp:505-510) and the core then hands back what
-      // gi.x held: seeded, that is the carried grf_opt -- the reference's
-      // result -- and not LDS this block never wrote.
-      P.gi.x[r] = prev;
-    }
-  }
-  GI_SYNC();
-  // swing-leg equality pattern AA (:310-350)
-  const int pat = force_pattern(a.mode[inst], a.right_support[inst]);
-  double f;
-  int st, it;
-  gi_solve_group<GW>(P.gi, li, 12, 12, 24, PG, 12, Pg0, c_force_CE[pat], c_force_zeros,
-                 ForceCi{a.mu, a.fz_max}, P.gi.x,
-                 f, st, it);
-  GI_SYNC();
-  // QPBaseClass::solveQP: success iff no NaN (go1_rt_control QPBaseClass.cpp:116-142); Solve / fallback
-  bool ok = true;
-  for (int k = 0; k < 12; ++k) ok = ok && !isnan(P.gi.x[k]);
-#pragma unroll
-  for (int v = 0; v < VL; ++v) {
-    const int r = li + GW * v;
-    if (r < 12) {
-      a.grf_opt[inst * 12 + r] = ok ? P.gi.x[r] : guess[v];
-      a.F_leg_guess[inst * 12 + r] = guess[v];
-      a.F_leg_ref[inst * 12 + r] = guess[v];  // = Fref (F_leg_guess := F_leg_ref, :251-260)
-    }
-  }
-  if (li == 0) {
-    if (a.qp_solution) a.qp_solution[inst] = ok ? 1 : 0;
-    if (a.status) a.status[inst] = st;
-    if (a.iters) a.iters[inst] = it;
-    if (a.prev_it) a.prev_it[inst] = it;
-  }
+// the caller-visible tau and grf_opt rows of a refused robot (the force block, the servo tick)
+__global__ __launch_bounds__(256) void force_body_mark_kernel(int64_t batch, const qloco_force_body *rows,
+                                                              double *tau, double *grf_opt) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= batch * 12) return;
+  if (force_body_ok(reinterpret_cast<const double *>(rows + t / 12))) return;
+  tau[t] = __longlong_as_double(0x7ff8000000000000ll);
+  grf_opt[t] = __longlong_as_double(0x7ff8000000000000ll);
+}
+
+int force_body_mark_refused(int64_t batch, const qloco_force_body *rows, double *tau, double *grf_opt,
+                            hipStream_t stream) {
+  const int64_t n = batch * 12;
+  hipLaunchKernelGGL(force_body_mark_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                     batch, rows, tau, grf_opt);
+  QLOCO_HIP_CHECK(hipGetLastError(), "force_body_mark_kernel launch");
+  return QLOCO_OK;
 }
 
 // dynmics_compute.cpp:109-138, one thread per (instance, leg)
@@ -468,15 +415,39 @@ extern "C" int64_t qloco_force_order_ws_len(int64_t batch) {
   return batch < 0 ? -1 : 2 * batch + 2 * kForceClasses;
 }
 
-extern "C" int qloco_force_qp_solve_ordered(const qloco_force_params *prm, int64_t batch,
-                                            const double *com_des, const double *leg_des,
-                                            const double *F_force_des, const double *rfoot_des,
-                                            const double *lfoot_des, const double *base_p,
-                                            const double *feet_p, const double *FT_total_des,
-                                            const int32_t *mode, const int32_t *right_support,
-                                            const double *y_coef, double *F_leg_ref, double *grf_opt,
-                                            double *F_leg_guess, int32_t *qp_solution, int32_t *status,
-                                            int32_t *iters, int32_t *order_ws, void *stream) {
+extern "C" int qloco_force_body_from_params(const qloco_force_params *p, int64_t count,
+                                            qloco_force_body *rows) {
+  if (!p || count < 0 || (count > 0 && !rows)) return QLOCO_ERR_ARG;
+  const double momentum[9] = QLOCO_MOMENTUM_SUM;
+  for (int64_t i = 0; i < count; ++i) {
+    qloco_force_body &r = rows[i];
+    r.mass = p->mass;
+    r.alpha = p->alpha;
+    r.beta = p->beta;
+    r.gamma = p->gamma;
+    r.fz_max = p->fz_max;
+    r.mu = p->mu;
+    memcpy(r.momentum, momentum, sizeof(momentum));
+    r.reserved[0] = 0.0;
+  }
+  return QLOCO_OK;
+}
+
+extern "C" int qloco_force_body_check(const qloco_force_body *row) {
+  if (!row) return QLOCO_ERR_ARG;
+  return force_body_ok(reinterpret_cast<const double *>(row)) ? QLOCO_OK : QLOCO_ERR_ARG;
+}
+
+extern "C" int qloco_force_qp_solve_body(const qloco_force_params *prm, int64_t batch,
+                                         const double *com_des, const double *leg_des,
+                                         const double *F_force_des, const double *rfoot_des,
+                                         const double *lfoot_des, const double *base_p,
+                                         const double *feet_p, const double *FT_total_des,
+                                         const int32_t *mode, const int32_t *right_support,
+                                         const double *y_coef, double *F_leg_ref, double *grf_opt,
+                                         double *F_leg_guess, int32_t *qp_solution, int32_t *status,
+                                         int32_t *iters, int32_t *order_ws,
+                                         const qloco_force_body *body, void *stream) {
   if (!prm || batch < 0) return QLOCO_ERR_ARG;
   if (batch == 0) return QLOCO_OK;
   if (!com_des || !leg_des || !F_force_des || !rfoot_des || !lfoot_des || !base_p || !feet_p ||
@@ -528,13 +499,30 @@ extern "C" int qloco_force_qp_solve_ordered(const qloco_force_params *prm, int64
   }
   if (g_force_gw.load(std::memory_order_relaxed) == 16) {
     const unsigned blocks = (unsigned)((batch + 3) / 4);
-    hipLaunchKernelGGL(force_qp_kernel<16>, dim3(blocks), dim3(64), 0, st, a);
+    if (body) hipLaunchKernelGGL(force_qp_body_kernel<16>, dim3(blocks), dim3(64), 0, st, a, body);
+    else hipLaunchKernelGGL(force_qp_kernel<16>, dim3(blocks), dim3(64), 0, st, a);
   } else {
     const unsigned blocks = (unsigned)((batch + 7) / 8);
-    hipLaunchKernelGGL(force_qp_kernel<8>, dim3(blocks), dim3(64), 0, st, a);
+    if (body) hipLaunchKernelGGL(force_qp_body_kernel<8>, dim3(blocks), dim3(64), 0, st, a, body);
+    else hipLaunchKernelGGL(force_qp_kernel<8>, dim3(blocks), dim3(64), 0, st, a);
   }
   QLOCO_HIP_CHECK(hipGetLastError(), "force_qp_kernel launch");
   return QLOCO_OK;
+}
+
+extern "C" int qloco_force_qp_solve_ordered(const qloco_force_params *prm, int64_t batch,
+                                            const double *com_des, const double *leg_des,
+                                            const double *F_force_des, const double *rfoot_des,
+                                            const double *lfoot_des, const double *base_p,
+                                            const double *feet_p, const double *FT_total_des,
+                                            const int32_t *mode, const int32_t *right_support,
+                                            const double *y_coef, double *F_leg_ref, double *grf_opt,
+                                            double *F_leg_guess, int32_t *qp_solution, int32_t *status,
+                                            int32_t *iters, int32_t *order_ws, void *stream) {
+  return qloco_force_qp_solve_body(prm, batch, com_des, leg_des, F_force_des, rfoot_des, lfoot_des,
+                                   base_p, feet_p, FT_total_des, mode, right_support, y_coef,
+                                   F_leg_ref, grf_opt, F_leg_guess, qp_solution, status, iters,
+                                   order_ws, nullptr, stream);
 }
 
 extern "C" int qloco_force_qp_solve(const qloco_force_params *prm, int64_t batch,
@@ -546,10 +534,10 @@ extern "C" int qloco_force_qp_solve(const qloco_force_params *prm, int64_t batch
                                     const double *y_coef, double *F_leg_ref, double *grf_opt,
                                     double *F_leg_guess, int32_t *qp_solution, int32_t *status,
                                     int32_t *iters, void *stream) {
-  return qloco_force_qp_solve_ordered(prm, batch, com_des, leg_des, F_force_des, rfoot_des, lfoot_des,
-                                      base_p, feet_p, FT_total_des, mode, right_support, y_coef,
-                                      F_leg_ref, grf_opt, F_leg_guess, qp_solution, status, iters,
-                                      nullptr, stream);
+  return qloco_force_qp_solve_body(prm, batch, com_des, leg_des, F_force_des, rfoot_des, lfoot_des,
+                                   base_p, feet_p, FT_total_des, mode, right_support, y_coef,
+                                   F_leg_ref, grf_opt, F_leg_guess, qp_solution, status, iters,
+                                   nullptr, nullptr, stream);
 }
 
 extern "C" int qloco_joint_torques(int64_t batch, const double *Jaco, const int32_t *swing,

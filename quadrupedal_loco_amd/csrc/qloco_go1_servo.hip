@@ -43,9 +43,7 @@ namespace go1servo {
 constexpr double MASS = 12.0;  // gait::mass (go1_rt_control Robotpara :29)
 constexpr double G = 9.8;      // gait::_g (:48)
 // Momentum_sum, servo.cpp:375-377 (row-major)
-__constant__ double c_momentum[9] = {2 * 0.0168352186, 2 * 0.0004636141, 2 * 0.0002367952,
-                                     2 * 0.0004636141, 2 * 0.0656071082, 2 * 3.6671e-05,
-                                     2 * 0.0002367952, 2 * 3.6671e-05,   2 * 0.0742720659};
+__constant__ double c_momentum[9] = QLOCO_MOMENTUM_SUM;
 
 constexpr int NF = QLOCO_GO1_SERVO_FILTERS;
 
@@ -147,6 +145,11 @@ struct TickArgs {
   double target[12];
   double percent, dtx, t_walk_start, pitch_w, half_hip;
   int n_t_int, n_period, ros_gt1;
+  // per-robot bodies (qloco_go1_servo_tick_body) or NULL, read by the gait
+  // branch only: mass and momentum of F_sum.  A refused row takes the constants
+  // as a stand-in, so nothing non-finite enters the workspace; the force QP
+  // refuses the robot.
+  const qloco_force_body *body;
 };
 
 template <bool HOMING>
@@ -317,13 +320,23 @@ __global__ __launch_bounds__(256) void go1_servo_kernel(const TickArgs a) {
       D(L.rel)[g3 + c] = rel[c];
     }
     double F_sum[6];
-    F_sum[0] = MASS * ca[0];
-    F_sum[1] = MASS * ca[1];
-    F_sum[2] = MASS * G + MASS * ca[2];
+    double mass = MASS, mom[9];
+#pragma unroll
+    for (int c = 0; c < 9; ++c) mom[c] = c_momentum[c];
+    if (a.body) {
+      const double *row = reinterpret_cast<const double *>(a.body + r);
+      if (force_body_ok(row)) {
+        mass = row[0];
+#pragma unroll
+        for (int c = 0; c < 9; ++c) mom[c] = row[6 + c];
+      }
+    }
+    F_sum[0] = mass * ca[0];
+    F_sum[1] = mass * ca[1];
+    F_sum[2] = mass * G + mass * ca[2];  // mass * G: MASS * G as the compiler folded it when mass = 12
 #pragma unroll
     for (int i = 0; i < 3; ++i)
-      F_sum[3 + i] = c_momentum[3 * i + 0] * ca[0] + c_momentum[3 * i + 1] * ca[1] +
-                     c_momentum[3 * i + 2] * ca[2];
+      F_sum[3 + i] = mom[3 * i + 0] * ca[0] + mom[3 * i + 1] * ca[1] + mom[3 * i + 2] * ca[2];
     const double v0 = lf[0] - rf[0], v1 = lf[1] - rf[1], v2 = lf[2] - rf[2];
     const double c0 = com[0] - rf[0], c1 = com[1] - rf[1], c2 = com[2] - rf[2];
     const double rlleg_dis = sqrt(v0 * v0 + v1 * v1 + v2 * v2);
@@ -601,13 +614,14 @@ extern "C" int qloco_go1_servo_init(const qloco_go1_servo_params *prm, int64_t b
   return QLOCO_OK;
 }
 
-extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t batch,
-                                    void *workspace, int64_t n_count, const double *q_mea,
-                                    const double *quat, const double *gait_msg,
-                                    const int32_t *gait_mode, const double *y_offset,
-                                    double *q_cmd, double *ctrl_msg, double *tau, double *grf_opt,
-                                    const qloco_go1_servo_diag *diag, double *gait_data,
-                                    void *stream) {
+extern "C" int qloco_go1_servo_tick_body(const qloco_go1_servo_params *prm, int64_t batch,
+                                         void *workspace, int64_t n_count, const double *q_mea,
+                                         const double *quat, const double *gait_msg,
+                                         const int32_t *gait_mode, const double *y_offset,
+                                         double *q_cmd, double *ctrl_msg, double *tau,
+                                         double *grf_opt, const qloco_go1_servo_diag *diag,
+                                         double *gait_data, const qloco_force_body *body,
+                                         void *stream) {
   if (!go1servo::params_ok(prm) || batch <= 0 || batch > (INT32_MAX >> 2) || n_count < 0 ||
       n_count >= INT32_MAX || !workspace || !q_mea || !quat || !gait_msg || !gait_mode ||
       !y_offset || !q_cmd || !ctrl_msg || !tau || !grf_opt)
@@ -640,6 +654,7 @@ extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t b
   const bool homing = t <= prm->stand_duration;  // :769
   const double frac = t / prm->stand_duration;
   a.percent = frac * frac;  // pow(v, 2): the exactly rounded square
+  a.body = homing ? nullptr : body;
   const dim3 grid((unsigned)((4 * batch + 255) / 256)), block(256);
   if (homing) {
     hipLaunchKernelGGL(go1servo::go1_servo_kernel<true>, grid, block, 0, st, a);
@@ -653,11 +668,11 @@ extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t b
     const double *bp = (const double *)(w + L.bpdes), *fd = (const double *)(w + L.fdes);
     const double *rf = (const double *)(w + L.ref[1]), *lf = (const double *)(w + L.ref[2]);
     double *fref = (double *)(w + L.fref);
-    int rc = qloco_force_qp_solve_ordered(
+    int rc = qloco_force_qp_solve_body(
         &prm->force, batch, bp, fd, (const double *)(w + L.flr), rf, lf, bp, fd,
         (const double *)(w + L.fsum), gait_mode, (const int32_t *)(w + L.rs), y_offset, fref,
         (double *)(w + L.grf), (double *)(w + L.guess), (int32_t *)(w + L.qps),
-        (int32_t *)(w + L.st), nullptr, (int32_t *)(w + L.ord), stream);
+        (int32_t *)(w + L.st), nullptr, (int32_t *)(w + L.ord), body, stream);
     if (rc != QLOCO_OK) return rc;
     // compute_joint_torques for FR, FL, RR, RL (:1232-1248)
     rc = qloco_joint_torques(batch, (const double *)(w + L.jaco), (const int32_t *)(w + L.swing),
@@ -672,6 +687,11 @@ extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t b
   QLOCO_HIP_CHECK(hipMemcpyAsync(grf_opt, w + L.grf, sizeof(double) * 12 * batch,
                                  hipMemcpyDeviceToDevice, st),
                   "grf_opt copy");
+  // a refused robot's workspace rows are finite (they did not move); what the caller sees is NaN
+  if (a.body) {
+    const int rc = force_body_mark_refused(batch, body, tau, grf_opt, st);
+    if (rc != QLOCO_OK) return rc;
+  }
   if (diag && diag->qp_solution)
     QLOCO_HIP_CHECK(hipMemcpyAsync(diag->qp_solution, w + L.qps, sizeof(int32_t) * batch,
                                    hipMemcpyDeviceToDevice, st),
@@ -688,6 +708,18 @@ extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t b
     QLOCO_HIP_CHECK(hipGetLastError(), "go1_gait_data_kernel launch");
   }
   return QLOCO_OK;
+}
+
+extern "C" int qloco_go1_servo_tick(const qloco_go1_servo_params *prm, int64_t batch,
+                                    void *workspace, int64_t n_count, const double *q_mea,
+                                    const double *quat, const double *gait_msg,
+                                    const int32_t *gait_mode, const double *y_offset,
+                                    double *q_cmd, double *ctrl_msg, double *tau, double *grf_opt,
+                                    const qloco_go1_servo_diag *diag, double *gait_data,
+                                    void *stream) {
+  return qloco_go1_servo_tick_body(prm, batch, workspace, n_count, q_mea, quat, gait_msg, gait_mode,
+                                   y_offset, q_cmd, ctrl_msg, tau, grf_opt, diag, gait_data, nullptr,
+                                   stream);
 }
 
 extern "C" int qloco_go1_servo_get_state(int64_t batch, const void *workspace, double *state,

@@ -25,9 +25,7 @@ constexpr double DTX = 0.005;   // gait::t_program_cyclic (go1_rt_control Robotp
 constexpr double MASS = 12.0;   // gait::mass (:29)
 constexpr double G = 9.8;       // gait::_g (:48)
 // Momentum_sum, servo.cpp:375-377 (row-major)
-__constant__ double c_momentum[9] = {2 * 0.0168352186, 2 * 0.0004636141, 2 * 0.0002367952,
-                                     2 * 0.0004636141, 2 * 0.0656071082, 2 * 3.6671e-05,
-                                     2 * 0.0002367952, 2 * 3.6671e-05,   2 * 0.0742720659};
+__constant__ double c_momentum[9] = QLOCO_MOMENTUM_SUM;
 
 struct Ws {  // byte offsets
   int64_t fref, grf, guess, rel, rold, vrel, fsum, flr, swing, qps, st, ord, total;
@@ -58,6 +56,10 @@ struct GlueArgs {
   const int32_t *rs, *mode, *loop;
   double *F_sum_out, *FLR_out;
   int32_t *swing_out;
+  // per-robot bodies (qloco_servo_force_block_body) or NULL: mass and momentum
+  // of F_sum.  A refused row takes the constants as a stand-in, so nothing
+  // non-finite enters the workspace; the force QP refuses the robot.
+  const qloco_force_body *body;
 };
 
 __global__ __launch_bounds__(256) void servo_glue_kernel(const GlueArgs a) {
@@ -84,12 +86,20 @@ __global__ __launch_bounds__(256) void servo_glue_kernel(const GlueArgs a) {
   }
   // F_sum (:1080-1088)
   double F_sum[6];
-  F_sum[0] = MASS * ca[0];
-  F_sum[1] = MASS * ca[1];
-  F_sum[2] = MASS * G + MASS * ca[2];
+  double mass = MASS, mom[9];
+  for (int k = 0; k < 9; ++k) mom[k] = c_momentum[k];
+  if (a.body) {
+    const double *row = reinterpret_cast<const double *>(a.body + r);
+    if (force_body_ok(row)) {
+      mass = row[0];
+      for (int k = 0; k < 9; ++k) mom[k] = row[6 + k];
+    }
+  }
+  F_sum[0] = mass * ca[0];
+  F_sum[1] = mass * ca[1];
+  F_sum[2] = mass * G + mass * ca[2];  // mass * G: MASS * G as the compiler folded it when mass = 12
   for (int i = 0; i < 3; ++i)
-    F_sum[3 + i] = c_momentum[3 * i + 0] * ca[0] + c_momentum[3 * i + 1] * ca[1] +
-                   c_momentum[3 * i + 2] * ca[2];
+    F_sum[3 + i] = mom[3 * i + 0] * ca[0] + mom[3 * i + 1] * ca[1] + mom[3 * i + 2] * ca[2];
   // rleg_com (:1097-1111), pow(v, 2) as v * v (oracle/servo_block.c)
   const double v0 = lf[0] - rf[0], v1 = lf[1] - rf[1], v2 = lf[2] - rf[2];
   const double c0 = cd[0] - rf[0], c1 = cd[1] - rf[1], c2 = cd[2] - rf[2];
@@ -161,14 +171,14 @@ extern "C" int qloco_servo_init(int64_t batch, void *workspace, void *stream) {
   return QLOCO_OK;
 }
 
-extern "C" int qloco_servo_force_block(
+extern "C" int qloco_servo_force_block_body(
     const qloco_force_params *prm, int64_t batch, void *workspace, const double *coma_des,
     const double *com_des, const double *rfoot_des, const double *lfoot_des,
     const double *body_p_des, const double *foot_des, const int32_t *right_support,
     const int32_t *gait_mode, const double *y_offset, const int32_t *loop_count,
     const double *Jaco, const double *foot_rel_mea, const double *v_est_rel, double *F_sum,
     double *Force_L_R, double *grf_opt, double *tau, int32_t *swing, int32_t *qp_solution,
-    int32_t *status, void *stream) {
+    int32_t *status, const qloco_force_body *body, void *stream) {
   if (!prm || batch < 0) return QLOCO_ERR_ARG;
   if (batch == 0) return QLOCO_OK;
   if (!workspace || !coma_des || !com_des || !rfoot_des || !lfoot_des || !body_p_des ||
@@ -193,6 +203,7 @@ extern "C" int qloco_servo_force_block(
   g.F_sum_out = F_sum;
   g.FLR_out = Force_L_R;
   g.swing_out = swing;
+  g.body = body;
   hipLaunchKernelGGL(servo::servo_glue_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256),
                      0, st, g);
   QLOCO_HIP_CHECK(hipGetLastError(), "servo_glue_kernel launch");
@@ -200,13 +211,13 @@ extern "C" int qloco_servo_force_block(
   // rfoot_des, lfoot_des); Dynam.force_opt(body_p_des, FR..RL_foot_des, F_sum, gait_mode,
   // right_support, y_offset)  (:1216-1228)
   double *fref = (double *)(w + L.fref), *grf = (double *)(w + L.grf);
-  int rc = qloco_force_qp_solve_ordered(prm, batch, body_p_des, foot_des, (const double *)(w + L.flr),
-                                        rfoot_des, lfoot_des, body_p_des, foot_des,
-                                        (const double *)(w + L.fsum), gait_mode, right_support, y_offset,
-                                        fref, grf, (double *)(w + L.guess),
-                                        qp_solution ? qp_solution : (int32_t *)(w + L.qps),
-                                        status ? status : (int32_t *)(w + L.st), nullptr,
-                                        (int32_t *)(w + L.ord), stream);
+  int rc = qloco_force_qp_solve_body(prm, batch, body_p_des, foot_des, (const double *)(w + L.flr),
+                                     rfoot_des, lfoot_des, body_p_des, foot_des,
+                                     (const double *)(w + L.fsum), gait_mode, right_support, y_offset,
+                                     fref, grf, (double *)(w + L.guess),
+                                     qp_solution ? qp_solution : (int32_t *)(w + L.qps),
+                                     status ? status : (int32_t *)(w + L.st), nullptr,
+                                     (int32_t *)(w + L.ord), body, stream);
   if (rc != QLOCO_OK) return rc;
   // compute_joint_torques for FR, FL, RR, RL (:1232-1243)
   rc = qloco_joint_torques(batch, Jaco, (const int32_t *)(w + L.swing), (const double *)(w + L.rel),
@@ -215,5 +226,21 @@ extern "C" int qloco_servo_force_block(
   QLOCO_HIP_CHECK(hipMemcpyAsync(grf_opt, grf, sizeof(double) * 12 * batch,
                                  hipMemcpyDeviceToDevice, st),
                   "grf_opt copy");
+  // a refused robot's tau is finite (its F_leg_ref did not move); what the caller sees is NaN
+  if (body) return force_body_mark_refused(batch, body, tau, grf_opt, st);
   return QLOCO_OK;
+}
+
+extern "C" int qloco_servo_force_block(
+    const qloco_force_params *prm, int64_t batch, void *workspace, const double *coma_des,
+    const double *com_des, const double *rfoot_des, const double *lfoot_des,
+    const double *body_p_des, const double *foot_des, const int32_t *right_support,
+    const int32_t *gait_mode, const double *y_offset, const int32_t *loop_count,
+    const double *Jaco, const double *foot_rel_mea, const double *v_est_rel, double *F_sum,
+    double *Force_L_R, double *grf_opt, double *tau, int32_t *swing, int32_t *qp_solution,
+    int32_t *status, void *stream) {
+  return qloco_servo_force_block_body(prm, batch, workspace, coma_des, com_des, rfoot_des, lfoot_des,
+                                      body_p_des, foot_des, right_support, gait_mode, y_offset,
+                                      loop_count, Jaco, foot_rel_mea, v_est_rel, F_sum, Force_L_R,
+                                      grf_opt, tau, swing, qp_solution, status, nullptr, stream);
 }

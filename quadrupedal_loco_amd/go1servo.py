@@ -25,7 +25,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import GO1_SERVO_DIAG, Go1ServoDiag, Go1ServoParams, check, lib, ptr
-from .qp import _stream
+from .qp import _body_arg, _stream
 
 STATE = 288           # QLOCO_GO1_SERVO_STATE
 GAIT_DATA_LEN = 100   # QLOCO_GO1_GAIT_DATA_LEN
@@ -118,8 +118,10 @@ class Go1ServoTick:
         p = self.params
         return n * (1.0 / p.rt_frequency) <= p.stand_duration
 
-    def step(self, q_mea, quat, gait_msg, gait_mode, y_offset):
-        """One loop iteration; increments n_count."""
+    def step(self, q_mea, quat, gait_msg, gait_mode, y_offset, body=None):
+        """One loop iteration; increments n_count.  body: (B, 16) float64
+        device rows of qp.force_body_rows, one per robot, read by the gait
+        branch only."""
         import torch
         q_mea = self._in(q_mea, "q_mea", 12, torch.float64)
         quat = self._in(quat, "quat", 4, torch.float64)
@@ -127,12 +129,13 @@ class Go1ServoTick:
         gait_mode = self._in(gait_mode, "gait_mode", 1, torch.int32)
         y_offset = self._in(y_offset, "y_offset", 1, torch.float64)
         o = self.out
+        body = _body_arg(body, self.batch, o["tau"])
         homing = self.homing()
-        check(lib().qloco_go1_servo_tick(
+        check(lib().qloco_go1_servo_tick_body(
             C.byref(self.params), self.batch, ptr(self.ws), self.n_count, ptr(q_mea), ptr(quat),
             ptr(gait_msg), ptr(gait_mode), ptr(y_offset), ptr(o["q_cmd"]), ptr(o["ctrl_msg"]),
             ptr(o["tau"]), ptr(o["grf_opt"]), C.byref(self.diag) if self.diag else None, ptr(o["gait_data"]),
-            _stream(self.ws)), "qloco_go1_servo_tick")
+            ptr(body), _stream(self.ws)), "qloco_go1_servo_tick_body")
         res = Go1ServoResult(o, homing, self.n_count)
         self.n_count += 1
         return res

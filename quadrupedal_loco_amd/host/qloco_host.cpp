@@ -260,6 +260,14 @@ void Dynamiccclass::force_opt(const double base_p[3], const double FR_p[3], cons
   if (r == batch_ - 1) run();
 }
 
+void Dynamiccclass::set_bodies(const qloco_force_body *host_rows) {
+  use_body_ = host_rows != nullptr;
+  if (!host_rows) return;
+  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
+  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
+  arena_.sync();  // the caller's rows may go away after the call
+}
+
 void Dynamiccclass::run() {
   const size_t B = batch_;
   arena_.upload(d_com_, h_com_.data(), sizeof(double) * B * 3);
@@ -273,10 +281,11 @@ void Dynamiccclass::run() {
   arena_.upload(d_y_, h_y_.data(), sizeof(double) * B);
   arena_.upload(d_mode_, h_mode_.data(), sizeof(int32_t) * B);
   arena_.upload(d_rs_, h_rs_.data(), sizeof(int32_t) * B);
-  abi_ok(qloco_force_qp_solve_ordered(&prm_, batch_, d_com_, d_leg_, d_F_, d_rf_, d_lf_, d_base_,
-                                      d_feet_, d_FT_, d_mode_, d_rs_, d_y_, d_Fref_, d_grf_, d_guess_,
-                                      d_qps_, d_st_, d_it_, d_ord_, arena_.stream()),
-         "qloco_force_qp_solve_ordered");
+  abi_ok(qloco_force_qp_solve_body(&prm_, batch_, d_com_, d_leg_, d_F_, d_rf_, d_lf_, d_base_,
+                                   d_feet_, d_FT_, d_mode_, d_rs_, d_y_, d_Fref_, d_grf_, d_guess_,
+                                   d_qps_, d_st_, d_it_, d_ord_, use_body_ ? d_body_ : nullptr,
+                                   arena_.stream()),
+         "qloco_force_qp_solve_body");
   arena_.download(grf_opt.data(), d_grf_, sizeof(double) * B * 12);
   arena_.download(F_leg_ref.data(), d_Fref_, sizeof(double) * B * 12);
   arena_.download(F_leg_guess.data(), d_guess_, sizeof(double) * B * 12);
@@ -1419,6 +1428,14 @@ ServoForceBlock::ServoForceBlock(int batch, const qloco_force_params *params) : 
   arena_.sync();
 }
 
+void ServoForceBlock::set_bodies(const qloco_force_body *host_rows) {
+  use_body_ = host_rows != nullptr;
+  if (!host_rows) return;
+  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
+  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
+  arena_.sync();  // the caller's rows may go away after the call
+}
+
 void ServoForceBlock::step(const double *coma_des, const double *com_des, const double *rfoot_des,
                            const double *lfoot_des, const double *body_p_des,
                            const double *foot_des, const int32_t *right_support,
@@ -1445,9 +1462,10 @@ void ServoForceBlock::step(const double *coma_des, const double *com_des, const 
   arena_.upload(cnt, count_in_rt_loop, sizeof(int32_t) * B);
   double *Fs = d_out_, *Fl = Fs + 6 * B, *g = Fl + 6 * B, *tau = g + 12 * B;
   int32_t *sw = d_iout_, *qps = sw + 4 * B, *st = qps + B;
-  abi_ok(qloco_servo_force_block(&prm_, batch_, d_ws_, coma, com, rf, lf, bp, ft, rs, md, y, cnt,
-                                 J, rm, ve, Fs, Fl, g, tau, sw, qps, st, arena_.stream()),
-         "qloco_servo_force_block");
+  abi_ok(qloco_servo_force_block_body(&prm_, batch_, d_ws_, coma, com, rf, lf, bp, ft, rs, md, y,
+                                      cnt, J, rm, ve, Fs, Fl, g, tau, sw, qps, st,
+                                      use_body_ ? d_body_ : nullptr, arena_.stream()),
+         "qloco_servo_force_block_body");
   arena_.download(F_sum.data(), Fs, sizeof(double) * 6 * B);
   arena_.download(Force_L_R.data(), Fl, sizeof(double) * 6 * B);
   arena_.download(grf_opt.data(), g, sizeof(double) * 12 * B);
@@ -1492,6 +1510,14 @@ Go1ServoBatch::Go1ServoBatch(int batch, const qloco_go1_servo_params *p)
   arena_.sync();
 }
 
+void Go1ServoBatch::set_bodies(const qloco_force_body *host_rows) {
+  use_body_ = host_rows != nullptr;
+  if (!host_rows) return;
+  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
+  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
+  arena_.sync();  // the caller's rows may go away after the call
+}
+
 void Go1ServoBatch::tick(const double *q_mea, const double *quat, const double *gait,
                          const int32_t *gait_mode, const double *y_offset) {
   if (!q_mea || !quat || !gait || !gait_mode || !y_offset)
@@ -1502,12 +1528,13 @@ void Go1ServoBatch::tick(const double *q_mea, const double *quat, const double *
   arena_.upload(d_in_ + kGI_GAIT * B, gait, sizeof(double) * QLOCO_GAIT_MSG_LEN * B);
   arena_.upload(d_in_ + kGI_Y * B, y_offset, sizeof(double) * B);
   arena_.upload(d_mode_, gait_mode, sizeof(int32_t) * B);
-  abi_ok(qloco_go1_servo_tick(&params, batch_, d_ws_, n_count, d_in_ + kGI_Q * B,
-                              d_in_ + kGI_QUAT * B, d_in_ + kGI_GAIT * B, d_mode_,
-                              d_in_ + kGI_Y * B, d_out_ + kGO_Q * B, d_out_ + kGO_CTRL * B,
-                              d_out_ + kGO_TAU * B, d_out_ + kGO_GRF * B, nullptr,
-                              d_out_ + kGO_DATA * B, arena_.stream()),
-         "qloco_go1_servo_tick");
+  abi_ok(qloco_go1_servo_tick_body(&params, batch_, d_ws_, n_count, d_in_ + kGI_Q * B,
+                                   d_in_ + kGI_QUAT * B, d_in_ + kGI_GAIT * B, d_mode_,
+                                   d_in_ + kGI_Y * B, d_out_ + kGO_Q * B, d_out_ + kGO_CTRL * B,
+                                   d_out_ + kGO_TAU * B, d_out_ + kGO_GRF * B, nullptr,
+                                   d_out_ + kGO_DATA * B, use_body_ ? d_body_ : nullptr,
+                                   arena_.stream()),
+         "qloco_go1_servo_tick_body");
   arena_.download(q_cmd.data(), d_out_ + kGO_Q * B, sizeof(double) * 12 * B);
   arena_.download(state_to_MPC.data(), d_out_ + kGO_CTRL * B, sizeof(double) * QLOCO_CTRL_MSG_LEN * B);
   arena_.download(Legs_torque.data(), d_out_ + kGO_TAU * B, sizeof(double) * 12 * B);

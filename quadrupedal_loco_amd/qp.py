@@ -15,9 +15,12 @@ libqloco.so and there is no host fallback.
 """
 import ctypes as C
 
-from ._lib import ForceParams, check, lib, ptr
+from ._lib import ForceBody, ForceParams, check, lib, ptr
 
 STATE_LEN = 32  # QLOCO_BODY_STATE_LEN
+FORCE_BODY_LEN = 16  # doubles of a qloco_force_body row
+FORCE_BODY_COLUMNS = {"mass": (0, 1), "alpha": (1, 2), "beta": (2, 3), "gamma": (3, 4),
+                      "fz_max": (4, 5), "mu": (5, 6), "momentum": (6, 15)}
 
 
 def _stream(t):
@@ -89,6 +92,69 @@ def force_params(hw=False, **kw):
     return p
 
 
+def force_body_rows(batch, params=None, **fields):
+    """Per-robot bodies for ForceQP.step / ServoForceBlock.step /
+    Go1ServoTick.step(body=): a (B, 16) float64 host array in qloco_force_body's
+    layout (mass | alpha | beta | gamma | fz_max | mu | momentum[9] row-major |
+    one reserved zero), every row filled from `params` (default:
+    force_params()) by qloco_force_body_from_params.  `fields` then overwrite
+    whole fields by name: a scalar (or, for momentum, its 9 values) for every
+    robot, or a per-robot array, (B,) for a scalar field and (B, 9) for
+    momentum.  Edit single rows in place, then move the array to the device
+    (torch.from_numpy(rows).to(dev))."""
+    import numpy as np
+    B = int(batch)
+    rows = np.zeros((B, FORCE_BODY_LEN), np.float64)
+    p = params if params is not None else force_params()
+    check(lib().qloco_force_body_from_params(C.byref(p), B, rows.ctypes.data_as(C.POINTER(ForceBody))),
+          "qloco_force_body_from_params")
+    for name, v in fields.items():
+        if name not in FORCE_BODY_COLUMNS:
+            raise ValueError("force_body_rows: unknown field %r (one of %s)"
+                             % (name, sorted(FORCE_BODY_COLUMNS)))
+        lo, hi = FORCE_BODY_COLUMNS[name]
+        a = np.asarray(v, dtype=np.float64)
+        if a.ndim == 1 and hi - lo == 1:
+            a = a.reshape(-1, 1)          # (B,) of a scalar field
+        rows[:, lo:hi] = np.broadcast_to(a, (B, hi - lo))
+    return rows
+
+
+def force_body_rows_from_srbd(model_rows, params=None):
+    """Rows for a fleet described by srbd.model_rows: mass, mu and fz_max from
+    its float32 columns, widened exactly; gains and momentum from `params` and
+    the defaults.  One fleet description then serves the MPC and the servo."""
+    import numpy as np
+    from .srbd import MODEL_COLUMNS
+    m = np.asarray(model_rows)
+    if m.ndim != 2 or m.shape[1] != 16 or m.dtype != np.float32:
+        raise ValueError("model_rows: a (B, 16) float32 array of srbd.model_rows expected")
+    col = lambda k: m[:, MODEL_COLUMNS[k][0]].astype(np.float64)
+    return force_body_rows(len(m), params, mass=col("mass"), mu=col("mu"), fz_max=col("fz_max"))
+
+
+def check_force_body(row):
+    """The row rule on one row of force_body_rows (qloco_force_body_check)."""
+    import numpy as np
+    r = np.ascontiguousarray(row, np.float64)
+    if r.shape != (FORCE_BODY_LEN,):
+        raise ValueError("row: %d doubles expected" % FORCE_BODY_LEN)
+    if lib().qloco_force_body_check(r.ctypes.data_as(C.POINTER(ForceBody))) != 0:
+        raise ValueError("qloco_force_body_check refuses the row")
+
+
+def _body_arg(body, batch, like):
+    """A (B, 16) float64 device tensor of qloco_force_body rows, or None."""
+    import torch
+    if body is None:
+        return None
+    if (not torch.is_tensor(body) or body.dtype != torch.float64 or not body.is_contiguous()
+            or body.device != like.device or tuple(body.shape) != (batch, FORCE_BODY_LEN)):
+        raise ValueError("body: a contiguous (%d, %d) float64 tensor on %s expected"
+                         % (batch, FORCE_BODY_LEN, like.device))
+    return body
+
+
 def hw_torque_ff(Jaco, grf_opt, grf_base, dynamic_count, stream=None):
     """The hardware loop's joint feed-forward after force_opt
     (unitree_legged_real torque_mode.cpp:1370-1384): stand-up ramp
@@ -131,14 +197,16 @@ class ForceQP:
                                      device=device) if grouped else None)
 
     def step(self, com_des, leg_des, F_force_des, rfoot_des, lfoot_des, base_p, feet_p,
-             FT_total_des, mode, right_support, y_coef):
-        """servo.cpp:1224-1228: force_distribution(...) then force_opt(...)."""
-        check(lib().qloco_force_qp_solve_ordered(
+             FT_total_des, mode, right_support, y_coef, body=None):
+        """servo.cpp:1224-1228: force_distribution(...) then force_opt(...).
+        body: (B, 16) float64 device rows of force_body_rows, one per robot."""
+        body = _body_arg(body, self.batch, self.F_leg_ref)
+        check(lib().qloco_force_qp_solve_body(
             C.byref(self.params), self.batch, ptr(com_des), ptr(leg_des), ptr(F_force_des),
             ptr(rfoot_des), ptr(lfoot_des), ptr(base_p), ptr(feet_p), ptr(FT_total_des),
             ptr(mode), ptr(right_support), ptr(y_coef), ptr(self.F_leg_ref), ptr(self.grf_opt),
             ptr(self.F_leg_guess), ptr(self.qp_solution), ptr(self.status), ptr(self.iters),
-            ptr(self.order_ws), _stream(com_des)), "qloco_force_qp_solve_ordered")
+            ptr(self.order_ws), ptr(body), _stream(com_des)), "qloco_force_qp_solve_body")
         return {"grf_opt": self.grf_opt, "F_leg_guess": self.F_leg_guess,
                 "F_leg_ref": self.F_leg_ref, "qp_solution": self.qp_solution,
                 "status": self.status, "iters": self.iters}
@@ -210,15 +278,17 @@ class ServoForceBlock:
         check(lib().qloco_servo_init(self.batch, ptr(self.ws), _stream(self.ws)), "qloco_servo_init")
 
     def step(self, coma_des, com_des, rfoot_des, lfoot_des, body_p_des, foot_des, right_support,
-             gait_mode, y_offset, loop_count, Jaco, foot_rel_mea, v_est_rel):
+             gait_mode, y_offset, loop_count, Jaco, foot_rel_mea, v_est_rel, body=None):
+        """body: (B, 16) float64 device rows of force_body_rows, one per robot."""
         o = self.out
-        check(lib().qloco_servo_force_block(
+        body = _body_arg(body, self.batch, o["tau"])
+        check(lib().qloco_servo_force_block_body(
             C.byref(self.params), self.batch, ptr(self.ws), ptr(coma_des), ptr(com_des),
             ptr(rfoot_des), ptr(lfoot_des), ptr(body_p_des), ptr(foot_des), ptr(right_support),
             ptr(gait_mode), ptr(y_offset), ptr(loop_count), ptr(Jaco), ptr(foot_rel_mea),
             ptr(v_est_rel), ptr(o["F_sum"]), ptr(o["Force_L_R"]), ptr(o["grf_opt"]), ptr(o["tau"]),
-            ptr(o["swing"]), ptr(o["qp_solution"]), ptr(o["status"]), _stream(self.ws)),
-            "qloco_servo_force_block")
+            ptr(o["swing"]), ptr(o["qp_solution"]), ptr(o["status"]), ptr(body), _stream(self.ws)),
+            "qloco_servo_force_block_body")
         return o
 
 
