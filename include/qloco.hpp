@@ -80,6 +80,28 @@ class DeviceArena {
   std::vector<void *> blocks_;
 };
 
+// Per-robot rows (set_bodies / set_models) in a block of the owner's arena.
+// set() copies `batch` host rows to the device now, allocating the block on
+// first use; nullptr switches the rows off and keeps the block.  get() is the
+// pointer the C ABI takes: nullptr while the rows are off.
+template <class T>
+class DeviceRows {
+ public:
+  void set(DeviceArena &arena, int batch, const T *host_rows) {
+    on_ = host_rows != nullptr;
+    if (!on_) return;
+    const size_t bytes = sizeof(T) * (size_t)batch;
+    if (!dev_) dev_ = static_cast<T *>(arena.alloc(bytes));
+    arena.upload(dev_, host_rows, bytes);
+    arena.sync();  // the caller's rows may go away after the call
+  }
+  const T *get() const { return on_ ? dev_ : nullptr; }
+
+ private:
+  T *dev_ = nullptr;
+  bool on_ = false;
+};
+
 // ------------------------------------------------------------------------
 // QPsolver / QPsolver_EiQuadProg (QPBaseClass.cpp:20-56): min 0.5 x'Gx + g0'x
 // s.t. CE'x + ce0 = 0, CI'x + ci0 >= 0 (EiQuadProg.hpp:15-36), quirk-compatible
@@ -148,7 +170,7 @@ class Dynamiccclass {
   // first use); run() then solves robot b with
   // its row's alpha, beta, gamma, fz_max and mu.  nullptr returns to params.  A robot
   // with a refused row gets status QLOCO_ERR_ARG and keeps its members.
-  void set_bodies(const qloco_force_body *host_rows);
+  void set_bodies(const qloco_force_body *host_rows) { body_.set(arena_, batch_, host_rows); }
   // compute_joint_torques for all legs of all robots (dynmics_compute.cpp:109-138)
   void compute_joint_torques(const double *Jaco /*B*4*9*/, const int32_t *swing /*B*4*/,
                              const double *p_des, const double *p_est, const double *pv_des,
@@ -170,8 +192,7 @@ class Dynamiccclass {
       *d_grf_, *d_guess_;
   int32_t *d_mode_, *d_rs_, *d_qps_, *d_st_, *d_it_;
   int32_t *d_ord_;           // grouped-launch workspace (qloco_force_order_ws_len)
-  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
-  bool use_body_ = false;
+  DeviceRows<qloco_force_body> body_;  // set_bodies' rows
   double *d_jt_ = nullptr;   // joint-torque staging (allocated on first use)
   int32_t *d_sw_ = nullptr;
 };
@@ -260,7 +281,7 @@ class ConvexMpcBatch {
   // inertia, mu and fz_min / fz_max in place of the spec's.  nullptr returns
   // to the spec's body.  A robot with an invalid row gets status
   // QLOCO_ERR_ARG and keeps its previous forces (the NaN guard).
-  void set_models(const qloco_srbd_model *host_rows);
+  void set_models(const qloco_srbd_model *host_rows) { model_.set(arena_, batch_, host_rows); }
   // settings / weights may be edited between calls; horizon and warm_start
   // size the device buffers and are fixed at construction (a changed value
   // throws qloco::Error on the next call)
@@ -273,8 +294,7 @@ class ConvexMpcBatch {
   int horizon_ = 0, warm_mode_ = 0;
   DeviceArena arena_;
   float *d_x0_, *d_xr_, *d_feet_, *d_u0_, *d_rec_ = nullptr;
-  qloco_srbd_model *d_model_ = nullptr;  // set_models' rows (allocated on first use)
-  bool use_model_ = false;
+  DeviceRows<qloco_srbd_model> model_;  // set_models' rows
   uint8_t *d_ct_;
   int32_t *d_st_, *d_it_;
   // multi-GPU form
@@ -310,7 +330,7 @@ class A1QpBatch {
   // and f_min / f_max in place of params' (the solver settings stay params').
   // nullptr returns to params.  A robot with an invalid row gets status
   // QLOCO_ERR_ARG and NaN forces.
-  void set_bodies(const qloco_a1_body *host_rows);
+  void set_bodies(const qloco_a1_body *host_rows) { body_.set(arena_, batch_, host_rows); }
   qloco_a1_params params;
   std::vector<int32_t> status, iters;
 
@@ -318,8 +338,7 @@ class A1QpBatch {
   int batch_;
   DeviceArena arena_;
   double *d_state_, *d_forces_;
-  qloco_a1_body *d_body_ = nullptr;  // set_bodies' rows (allocated on first use)
-  bool use_body_ = false;
+  DeviceRows<qloco_a1_body> body_;  // set_bodies' rows
   uint8_t *d_ct_;
   int32_t *d_st_, *d_it_;
 };
@@ -653,7 +672,7 @@ class ServoForceBlock {
   // first use); step() then builds F_sum with
   // robot b's mass and momentum and solves with its row.  nullptr returns to params.  A robot
   // with a refused row gets status QLOCO_ERR_ARG and NaN grf_opt / Legs_torque.
-  void set_bodies(const qloco_force_body *host_rows);
+  void set_bodies(const qloco_force_body *host_rows) { body_.set(arena_, batch_, host_rows); }
   std::vector<double> F_sum, Force_L_R, grf_opt, Legs_torque;  // 6, 6, 12, 12 per robot
   std::vector<int32_t> swing, qp_solution, status;             // 4, 1, 1 per robot
   int batch() const { return batch_; }
@@ -665,8 +684,7 @@ class ServoForceBlock {
   void *d_ws_;
   double *d_in_, *d_out_;
   int32_t *d_iin_, *d_iout_;
-  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
-  bool use_body_ = false;
+  DeviceRows<qloco_force_body> body_;  // set_bodies' rows
 };
 
 // ------------------------------------------------------------------------
@@ -688,7 +706,7 @@ class Go1ServoBatch {
   // first use); the gait branch of tick() then
   // builds F_sum with robot b's mass and momentum and solves with its row.  nullptr returns to params.  A robot
   // with a refused row gets status QLOCO_ERR_ARG and NaN grf_opt / Legs_torque.
-  void set_bodies(const qloco_force_body *host_rows);
+  void set_bodies(const qloco_force_body *host_rows) { body_.set(arena_, batch_, host_rows); }
   std::vector<double> q_cmd;           // lowCmd.motorCmd[j].q, B*12
   std::vector<double> state_to_MPC;    // the /control2rtmpc/state row published at :762, B*25
   std::vector<double> state_feedback;  // the member after the tick ([0] = t_int), B*25
@@ -708,8 +726,7 @@ class Go1ServoBatch {
   void *d_ws_;
   double *d_in_, *d_out_, *d_rec_;
   int32_t *d_mode_;
-  qloco_force_body *d_body_ = nullptr;  // set_bodies' rows
-  bool use_body_ = false;
+  DeviceRows<qloco_force_body> body_;  // set_bodies' rows
 };
 
 }  // namespace qloco

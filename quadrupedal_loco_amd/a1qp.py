@@ -21,6 +21,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import A1Body, A1Params, check, lib, ptr
+from ._rows import build_rows, check_row, rows_arg, rows_from_srbd
 
 STATE_LEN = 54  # QLOCO_A1_STATE_LEN
 
@@ -65,20 +66,10 @@ def body_rows(batch, params=None, **columns):
     6 values) for every robot, or a per-robot array, (B,) for a scalar field
     and (B, 3) / (B, 6) for a vector one.  Edit single rows in place, then move
     the array to the device (torch.from_numpy(rows).to(dev))."""
-    B = int(batch)
-    rows = np.zeros((B, BODY_LEN), np.float64)
     p = params if params is not None else default_params()
-    check(lib().qloco_a1_body_from_params(C.byref(p), B, rows.ctypes.data_as(C.POINTER(A1Body))),
-          "qloco_a1_body_from_params")
-    for name, v in columns.items():
-        if name not in BODY_COLUMNS:
-            raise ValueError("body_rows: unknown field %r (one of %s)" % (name, sorted(BODY_COLUMNS)))
-        lo, hi = BODY_COLUMNS[name]
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 1 and hi - lo == 1:
-            a = a.reshape(-1, 1)          # (B,) of a scalar field
-        rows[:, lo:hi] = np.broadcast_to(a, (B, hi - lo))
-    return rows
+    fill = lambda B, rows: check(lib().qloco_a1_body_from_params(
+        C.byref(p), B, rows.ctypes.data_as(C.POINTER(A1Body))), "qloco_a1_body_from_params")
+    return build_rows(batch, BODY_LEN, np.float64, BODY_COLUMNS, fill, columns, "body_rows")
 
 
 def body_rows_from_srbd(model_rows, params=None):
@@ -86,23 +77,14 @@ def body_rows_from_srbd(model_rows, params=None):
     per-robot bodies): robot_mass, mu, f_min and f_max from its float32 columns
     mass, mu, fz_min and fz_max, widened exactly; gains and weights from
     `params`.  One fleet description then serves both A1 branches."""
-    from .srbd import MODEL_COLUMNS
-    m = np.asarray(model_rows)
-    if m.ndim != 2 or m.shape[1] != 16 or m.dtype != np.float32:
-        raise ValueError("model_rows: a (B, 16) float32 array of srbd.model_rows expected")
-    col = lambda k: m[:, MODEL_COLUMNS[k][0]].astype(np.float64)
-    return body_rows(len(m), params, robot_mass=col("mass"), mu=col("mu"), f_min=col("fz_min"),
-                     f_max=col("fz_max"))
+    cols = rows_from_srbd(model_rows, dict(robot_mass="mass", mu="mu", f_min="fz_min", f_max="fz_max"))
+    return body_rows(len(cols["mu"]), params, **cols)
 
 
 def check_body(row):
     """The body half of the parameter rule on one row of body_rows
     (qloco_a1_body_check); ValueError naming the field."""
-    r = np.ascontiguousarray(row, np.float64)
-    if r.shape != (BODY_LEN,):
-        raise ValueError("row: %d doubles expected" % BODY_LEN)
-    if lib().qloco_a1_body_check(r.ctypes.data_as(C.POINTER(A1Body))) != 0:
-        raise ValueError(lib().qloco_last_error().decode())
+    check_row(row, BODY_LEN, A1Body, lib().qloco_a1_body_check, lambda: lib().qloco_last_error().decode())
 
 
 def _rot_zyx(roll, pitch, yaw):
@@ -188,12 +170,7 @@ class A1QpBatch:
         comes back with status QLOCO_ERR_ARG and NaN forces."""
         import torch
         B = state.shape[0]
-        if body is not None and (
-                not isinstance(body, torch.Tensor) or body.dtype != torch.float64
-                or not body.is_contiguous() or not body.is_cuda or body.device != state.device
-                or tuple(body.shape) != (B, BODY_LEN)):
-            raise ValueError("body: contiguous float64 (B, %d) tensor on the state's device expected"
-                             % BODY_LEN)
+        body = rows_arg(body, B, BODY_LEN, torch.float64, state.device)
         if (state.dtype != torch.float64 or not state.is_contiguous() or not state.is_cuda
                 or tuple(state.shape) != (B, STATE_LEN)):
             raise ValueError("state: contiguous float64 (B, %d) device tensor expected" % STATE_LEN)

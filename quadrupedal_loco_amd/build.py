@@ -50,9 +50,13 @@ SOURCES = [
 # Gauss-Jordan updates are written with explicit float2 ops).  Its pivot
 # loops are unrolled in full (static register per pivot column); the two-wave
 # inverse's body exceeds the default pragma-unroll budget, so it is raised.
-EXTRA = {"qloco_a1qp.hip": ["-ffp-contract=off"], "qloco_a1est.hip": ["-ffp-contract=off"], "qloco_a1ctrl.hip": ["-ffp-contract=off"], "qloco_nlp.hip": ["-ffp-contract=off"], "qloco_nlp_tick.hip": ["-ffp-contract=off"], "qloco_nlp_node.hip": ["-ffp-contract=off"], "qloco_gi.hip": ["-ffp-contract=off"], "qloco_gi_wide.hip": ["-ffp-contract=off"], "qloco_force.hip": ["-ffp-contract=off"],
-         "qloco_body.hip": ["-ffp-contract=off"], "qloco_rt.hip": ["-ffp-contract=off"], "qloco_servo.hip": ["-ffp-contract=off"], "qloco_go1_servo.hip": ["-ffp-contract=off"], "qloco_kin.hip": ["-ffp-contract=off"], "qloco_srbd.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"],
-         "qloco_srbd_lit.hip": ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"]}
+NO_CONTRACT = {"qloco_a1qp.hip", "qloco_a1est.hip", "qloco_a1ctrl.hip", "qloco_nlp.hip",
+               "qloco_nlp_tick.hip", "qloco_nlp_node.hip", "qloco_gi.hip", "qloco_gi_wide.hip",
+               "qloco_force.hip", "qloco_body.hip", "qloco_rt.hip", "qloco_servo.hip",
+               "qloco_go1_servo.hip", "qloco_kin.hip"}
+SRBD_FLAGS = ["-fno-slp-vectorize", "-mllvm", "-pragma-unroll-threshold=200000"]
+EXTRA = {**{src: ["-ffp-contract=off"] for src in NO_CONTRACT},
+         "qloco_srbd.hip": SRBD_FLAGS, "qloco_srbd_lit.hip": SRBD_FLAGS}
 
 COMMON = ["-O3", "-std=c++17", "-fPIC", "-I" + INCLUDE, "-I" + CSRC]
 
@@ -99,15 +103,8 @@ def build(verbose=False, jobs=8):
             print(" ".join(link))
         subprocess.run(link, check=True)
     build_host(verbose)
-    build_a1_est_host_test(verbose)
-    build_a1_ctrl_host_test(verbose)
-    build_nlp_host_test(verbose)
-    build_nlp_tick_host_test(verbose)
-    build_nlp_node_host_test(verbose)
-    build_go1_servo_host_test(verbose)
-    build_srbd_model_host_test(verbose)
-    build_a1qp_body_host_test(verbose)
-    build_force_body_host_test(verbose)
+    for name in HOST_EXES:
+        build_host_exe(name, verbose)
     return LIB
 
 
@@ -133,186 +130,38 @@ def build_host(verbose=False):
     return HOST_LIB
 
 
+# tests/cpp/<name>.cpp programs over the C++ shim that link no oracle
+HOST_EXES = ("test_a1_est_host", "test_a1_ctrl_host", "test_nlp_host", "test_nlp_tick_host",
+             "test_nlp_node_host", "test_go1_servo_host", "test_srbd_model_host",
+             "test_a1qp_body_host", "test_force_body_host")
+
+
+def build_host_exe(name, verbose=False, oracle_lib=None):
+    """tests/cpp/<name>.cpp -> tests/cpp/_build/<name>, linked against the shim
+    and libqloco.so; with `oracle_lib`, against the oracle as checker too."""
+    src = os.path.join(ROOT, "tests", "cpp", name + ".cpp")
+    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
+    os.makedirs(outdir, exist_ok=True)
+    exe = os.path.join(outdir, name)
+    if not _needs(exe, [src, HOST_LIB, LIB, oracle_lib or os.path.join(INCLUDE, "qloco.hpp")]):
+        return exe
+    inc = link = rpath = []
+    if oracle_lib:
+        inc = ["-I" + os.path.join(ROOT, "oracle")]
+        link = ["-L" + os.path.dirname(oracle_lib), "-lqloco_oracle"]
+        rpath = ["-Wl,-rpath,$ORIGIN/../../../oracle/_build"]
+    cmd = ([HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + inc +
+           [src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco"] + link +
+           ["-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + rpath + HIP_LINK)
+    if verbose:
+        print(" ".join(cmd))
+    subprocess.run(cmd, check=True)
+    return exe
+
+
 def build_host_test(oracle_lib, verbose=False):
     """tests/cpp/test_host (test infrastructure: links the oracle as checker)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, oracle_lib]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           "-I" + os.path.join(ROOT, "oracle"), src, "-o", exe, "-L" + LIBDIR, "-lqloco_host",
-           "-lqloco", "-L" + os.path.dirname(oracle_lib), "-lqloco_oracle",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib",
-           "-Wl,-rpath,$ORIGIN/../../../oracle/_build"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_a1_est_host_test(verbose=False):
-    """tests/cpp/test_a1_est_host: the A1BasicEKFBatch shim against the C ABI
-    (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_a1_est_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_a1_est_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_a1_ctrl_host_test(verbose=False):
-    """tests/cpp/test_a1_ctrl_host: the A1RobotControlBatch shim against the C
-    ABI (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_a1_ctrl_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_a1_ctrl_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_nlp_host_test(verbose=False):
-    """tests/cpp/test_nlp_host: the NLPStepTimingBatch shim against the C ABI
-    (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_nlp_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_nlp_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_nlp_tick_host_test(verbose=False):
-    """tests/cpp/test_nlp_tick_host: the NLPClassBatch shim against the C ABI
-    (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_nlp_tick_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_nlp_tick_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_nlp_node_host_test(verbose=False):
-    """tests/cpp/test_nlp_node_host: the NLPRTControlBatch shim against the C
-    ABI (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_nlp_node_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_nlp_node_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_go1_servo_host_test(verbose=False):
-    """tests/cpp/test_go1_servo_host: the Go1ServoBatch shim against the C ABI
-    (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_go1_servo_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_go1_servo_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_srbd_model_host_test(verbose=False):
-    """tests/cpp/test_srbd_model_host: ConvexMpcBatch::set_models against
-    one-robot objects whose spec carries the row's values (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_srbd_model_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_srbd_model_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_a1qp_body_host_test(verbose=False):
-    """tests/cpp/test_a1qp_body_host: A1QpBatch::set_bodies against one-robot
-    objects whose params carry the row's values (no oracle link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_a1qp_body_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_a1qp_body_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
-
-
-def build_force_body_host_test(verbose=False):
-    """tests/cpp/test_force_body_host: set_bodies of Dynamiccclass,
-    ServoForceBlock and Go1ServoBatch against one-robot objects (no oracle
-    link)."""
-    src = os.path.join(ROOT, "tests", "cpp", "test_force_body_host.cpp")
-    outdir = os.path.join(ROOT, "tests", "cpp", "_build")
-    os.makedirs(outdir, exist_ok=True)
-    exe = os.path.join(outdir, "test_force_body_host")
-    if not _needs(exe, [src, HOST_LIB, LIB, os.path.join(INCLUDE, "qloco.hpp")]):
-        return exe
-    cmd = [HIPCC, "-x", "c++", "-O2", "-std=c++17", "-I" + INCLUDE] + HIP_HOST + [
-           src, "-o", exe, "-L" + LIBDIR, "-lqloco_host", "-lqloco",
-           "-Wl,-rpath,$ORIGIN/../../../quadrupedal_loco_amd/lib"] + HIP_LINK
-    if verbose:
-        print(" ".join(cmd))
-    subprocess.run(cmd, check=True)
-    return exe
+    return build_host_exe("test_host", verbose, oracle_lib)
 
 
 if __name__ == "__main__":

@@ -25,7 +25,8 @@ import ctypes as C
 import numpy as np
 
 from ._lib import GO1_SERVO_DIAG, Go1ServoDiag, Go1ServoParams, check, lib, ptr
-from .qp import _body_arg, _stream
+from ._rows import rows_arg
+from .qp import FORCE_BODY_LEN, _stream
 
 STATE = 288           # QLOCO_GO1_SERVO_STATE
 GAIT_DATA_LEN = 100   # QLOCO_GO1_GAIT_DATA_LEN
@@ -129,7 +130,7 @@ class Go1ServoTick:
         gait_mode = self._in(gait_mode, "gait_mode", 1, torch.int32)
         y_offset = self._in(y_offset, "y_offset", 1, torch.float64)
         o = self.out
-        body = _body_arg(body, self.batch, o["tau"])
+        body = rows_arg(body, self.batch, FORCE_BODY_LEN, torch.float64, o["tau"].device)
         homing = self.homing()
         check(lib().qloco_go1_servo_tick_body(
             C.byref(self.params), self.batch, ptr(self.ws), self.n_count, ptr(q_mea), ptr(quat),

@@ -260,14 +260,6 @@ void Dynamiccclass::force_opt(const double base_p[3], const double FR_p[3], cons
   if (r == batch_ - 1) run();
 }
 
-void Dynamiccclass::set_bodies(const qloco_force_body *host_rows) {
-  use_body_ = host_rows != nullptr;
-  if (!host_rows) return;
-  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
-  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
-  arena_.sync();  // the caller's rows may go away after the call
-}
-
 void Dynamiccclass::run() {
   const size_t B = batch_;
   arena_.upload(d_com_, h_com_.data(), sizeof(double) * B * 3);
@@ -283,8 +275,7 @@ void Dynamiccclass::run() {
   arena_.upload(d_rs_, h_rs_.data(), sizeof(int32_t) * B);
   abi_ok(qloco_force_qp_solve_body(&prm_, batch_, d_com_, d_leg_, d_F_, d_rf_, d_lf_, d_base_,
                                    d_feet_, d_FT_, d_mode_, d_rs_, d_y_, d_Fref_, d_grf_, d_guess_,
-                                   d_qps_, d_st_, d_it_, d_ord_, use_body_ ? d_body_ : nullptr,
-                                   arena_.stream()),
+                                   d_qps_, d_st_, d_it_, d_ord_, body_.get(), arena_.stream()),
          "qloco_force_qp_solve_body");
   arena_.download(grf_opt.data(), d_grf_, sizeof(double) * B * 12);
   arena_.download(F_leg_ref.data(), d_Fref_, sizeof(double) * B * 12);
@@ -467,14 +458,6 @@ void ConvexMpcBatch::reset() {
          "hipMemsetAsync");
 }
 
-void ConvexMpcBatch::set_models(const qloco_srbd_model *host_rows) {
-  use_model_ = host_rows != nullptr;
-  if (!host_rows) return;
-  if (!d_model_) d_model_ = dalloc<qloco_srbd_model>(arena_, (size_t)batch_);
-  arena_.upload(d_model_, host_rows, sizeof(qloco_srbd_model) * (size_t)batch_);
-  arena_.sync();  // the caller's rows may go away after the call
-}
-
 void ConvexMpcBatch::solve_device(const float *x0, const float *x_ref, const float *feet,
                                   const uint8_t *contacts, float *u0, int32_t *st, int32_t *it) {
   check_spec();
@@ -484,7 +467,7 @@ void ConvexMpcBatch::solve_device(const float *x0, const float *x_ref, const flo
   const int32_t legs = 4 * horizon_;  // constant contacts over the horizon: 4N worst case
   abi_ok(qloco_srbd_solve_model(&spec, batch_, x0, x_ref, feet, contacts, u0, nullptr, st, it,
                                 nullptr, nullptr, d_rec_, legs, nullptr,
-                                use_model_ ? d_model_ : nullptr, arena_.stream()),
+                                model_.get(), arena_.stream()),
          "qloco_srbd_solve_model");
 }
 
@@ -543,8 +526,7 @@ void ConvexMpcBatch::compute_grf(const A1MpcState *s, double *forces) {
   arena_.upload(d_ct_, ct.data(), B * 4);
   if (mg_) {  // this rank's shard, then one all-gather of every robot's u0
     abi_ok(qloco_mgpu_solve_model(mg_, &spec, d_x0_, d_xr_, d_feet_, d_ct_, d_rec_, d_u0_all_,
-                                  d_st_all_, d_it_all_, maxlegs, use_model_ ? d_model_ : nullptr,
-                                  arena_.stream()),
+                                  d_st_all_, d_it_all_, maxlegs, model_.get(), arena_.stream()),
            "qloco_mgpu_solve_model");
     const size_t T = (size_t)total_;
     std::vector<float> ua(T * 12);
@@ -573,7 +555,7 @@ void ConvexMpcBatch::compute_grf(const A1MpcState *s, double *forces) {
   }
   abi_ok(qloco_srbd_solve_model(&spec, batch_, d_x0_, d_xr_, d_feet_, d_ct_, d_u0_, nullptr, d_st_,
                                 d_it_, nullptr, nullptr, d_rec_, maxlegs, nullptr,
-                                use_model_ ? d_model_ : nullptr, arena_.stream()),
+                                model_.get(), arena_.stream()),
          "qloco_srbd_solve_model");
   std::vector<float> u0(B * 12);
   arena_.download(u0.data(), d_u0_, sizeof(float) * B * 12);
@@ -605,14 +587,6 @@ A1QpBatch::A1QpBatch(int batch, const qloco_a1_params *p)
   iters.assign(B, 0);
 }
 
-void A1QpBatch::set_bodies(const qloco_a1_body *host_rows) {
-  use_body_ = host_rows != nullptr;
-  if (!host_rows) return;
-  if (!d_body_) d_body_ = dalloc<qloco_a1_body>(arena_, (size_t)batch_);
-  arena_.upload(d_body_, host_rows, sizeof(qloco_a1_body) * (size_t)batch_);
-  arena_.sync();  // the caller's rows may go away after the call
-}
-
 void A1QpBatch::compute_grf(const A1QpState *s, double *forces) {
   const size_t B = batch_;
   std::vector<double> st(B * QLOCO_A1_STATE_LEN);
@@ -634,7 +608,7 @@ void A1QpBatch::compute_grf(const A1QpState *s, double *forces) {
   arena_.upload(d_state_, st.data(), sizeof(double) * st.size());
   arena_.upload(d_ct_, ct.data(), ct.size());
   abi_ok(qloco_a1_qp_solve_body(&params, batch_, d_state_, d_ct_, d_forces_, nullptr, d_st_, d_it_,
-                                nullptr, nullptr, use_body_ ? d_body_ : nullptr, arena_.stream()),
+                                nullptr, nullptr, body_.get(), arena_.stream()),
          "qloco_a1_qp_solve_body");
   arena_.download(forces, d_forces_, sizeof(double) * B * 12);
   arena_.download(status.data(), d_st_, sizeof(int32_t) * B);
@@ -1428,14 +1402,6 @@ ServoForceBlock::ServoForceBlock(int batch, const qloco_force_params *params) : 
   arena_.sync();
 }
 
-void ServoForceBlock::set_bodies(const qloco_force_body *host_rows) {
-  use_body_ = host_rows != nullptr;
-  if (!host_rows) return;
-  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
-  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
-  arena_.sync();  // the caller's rows may go away after the call
-}
-
 void ServoForceBlock::step(const double *coma_des, const double *com_des, const double *rfoot_des,
                            const double *lfoot_des, const double *body_p_des,
                            const double *foot_des, const int32_t *right_support,
@@ -1464,7 +1430,7 @@ void ServoForceBlock::step(const double *coma_des, const double *com_des, const 
   int32_t *sw = d_iout_, *qps = sw + 4 * B, *st = qps + B;
   abi_ok(qloco_servo_force_block_body(&prm_, batch_, d_ws_, coma, com, rf, lf, bp, ft, rs, md, y,
                                       cnt, J, rm, ve, Fs, Fl, g, tau, sw, qps, st,
-                                      use_body_ ? d_body_ : nullptr, arena_.stream()),
+                                      body_.get(), arena_.stream()),
          "qloco_servo_force_block_body");
   arena_.download(F_sum.data(), Fs, sizeof(double) * 6 * B);
   arena_.download(Force_L_R.data(), Fl, sizeof(double) * 6 * B);
@@ -1510,14 +1476,6 @@ Go1ServoBatch::Go1ServoBatch(int batch, const qloco_go1_servo_params *p)
   arena_.sync();
 }
 
-void Go1ServoBatch::set_bodies(const qloco_force_body *host_rows) {
-  use_body_ = host_rows != nullptr;
-  if (!host_rows) return;
-  if (!d_body_) d_body_ = dalloc<qloco_force_body>(arena_, (size_t)batch_);
-  arena_.upload(d_body_, host_rows, sizeof(qloco_force_body) * (size_t)batch_);
-  arena_.sync();  // the caller's rows may go away after the call
-}
-
 void Go1ServoBatch::tick(const double *q_mea, const double *quat, const double *gait,
                          const int32_t *gait_mode, const double *y_offset) {
   if (!q_mea || !quat || !gait || !gait_mode || !y_offset)
@@ -1532,8 +1490,7 @@ void Go1ServoBatch::tick(const double *q_mea, const double *quat, const double *
                                    d_in_ + kGI_QUAT * B, d_in_ + kGI_GAIT * B, d_mode_,
                                    d_in_ + kGI_Y * B, d_out_ + kGO_Q * B, d_out_ + kGO_CTRL * B,
                                    d_out_ + kGO_TAU * B, d_out_ + kGO_GRF * B, nullptr,
-                                   d_out_ + kGO_DATA * B, use_body_ ? d_body_ : nullptr,
-                                   arena_.stream()),
+                                   d_out_ + kGO_DATA * B, body_.get(), arena_.stream()),
          "qloco_go1_servo_tick_body");
   arena_.download(q_cmd.data(), d_out_ + kGO_Q * B, sizeof(double) * 12 * B);
   arena_.download(state_to_MPC.data(), d_out_ + kGO_CTRL * B, sizeof(double) * QLOCO_CTRL_MSG_LEN * B);

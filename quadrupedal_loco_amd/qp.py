@@ -16,6 +16,7 @@ libqloco.so and there is no host fallback.
 import ctypes as C
 
 from ._lib import ForceBody, ForceParams, check, lib, ptr
+from ._rows import build_rows, check_row, rows_arg, rows_from_srbd
 
 STATE_LEN = 32  # QLOCO_BODY_STATE_LEN
 FORCE_BODY_LEN = 16  # doubles of a qloco_force_body row
@@ -103,56 +104,24 @@ def force_body_rows(batch, params=None, **fields):
     momentum.  Edit single rows in place, then move the array to the device
     (torch.from_numpy(rows).to(dev))."""
     import numpy as np
-    B = int(batch)
-    rows = np.zeros((B, FORCE_BODY_LEN), np.float64)
     p = params if params is not None else force_params()
-    check(lib().qloco_force_body_from_params(C.byref(p), B, rows.ctypes.data_as(C.POINTER(ForceBody))),
-          "qloco_force_body_from_params")
-    for name, v in fields.items():
-        if name not in FORCE_BODY_COLUMNS:
-            raise ValueError("force_body_rows: unknown field %r (one of %s)"
-                             % (name, sorted(FORCE_BODY_COLUMNS)))
-        lo, hi = FORCE_BODY_COLUMNS[name]
-        a = np.asarray(v, dtype=np.float64)
-        if a.ndim == 1 and hi - lo == 1:
-            a = a.reshape(-1, 1)          # (B,) of a scalar field
-        rows[:, lo:hi] = np.broadcast_to(a, (B, hi - lo))
-    return rows
+    fill = lambda B, rows: check(lib().qloco_force_body_from_params(
+        C.byref(p), B, rows.ctypes.data_as(C.POINTER(ForceBody))), "qloco_force_body_from_params")
+    return build_rows(batch, FORCE_BODY_LEN, np.float64, FORCE_BODY_COLUMNS, fill, fields, "force_body_rows")
 
 
 def force_body_rows_from_srbd(model_rows, params=None):
     """Rows for a fleet described by srbd.model_rows: mass, mu and fz_max from
     its float32 columns, widened exactly; gains and momentum from `params` and
     the defaults.  One fleet description then serves the MPC and the servo."""
-    import numpy as np
-    from .srbd import MODEL_COLUMNS
-    m = np.asarray(model_rows)
-    if m.ndim != 2 or m.shape[1] != 16 or m.dtype != np.float32:
-        raise ValueError("model_rows: a (B, 16) float32 array of srbd.model_rows expected")
-    col = lambda k: m[:, MODEL_COLUMNS[k][0]].astype(np.float64)
-    return force_body_rows(len(m), params, mass=col("mass"), mu=col("mu"), fz_max=col("fz_max"))
+    cols = rows_from_srbd(model_rows, dict(mass="mass", mu="mu", fz_max="fz_max"))
+    return force_body_rows(len(cols["mu"]), params, **cols)
 
 
 def check_force_body(row):
     """The row rule on one row of force_body_rows (qloco_force_body_check)."""
-    import numpy as np
-    r = np.ascontiguousarray(row, np.float64)
-    if r.shape != (FORCE_BODY_LEN,):
-        raise ValueError("row: %d doubles expected" % FORCE_BODY_LEN)
-    if lib().qloco_force_body_check(r.ctypes.data_as(C.POINTER(ForceBody))) != 0:
-        raise ValueError("qloco_force_body_check refuses the row")
-
-
-def _body_arg(body, batch, like):
-    """A (B, 16) float64 device tensor of qloco_force_body rows, or None."""
-    import torch
-    if body is None:
-        return None
-    if (not torch.is_tensor(body) or body.dtype != torch.float64 or not body.is_contiguous()
-            or body.device != like.device or tuple(body.shape) != (batch, FORCE_BODY_LEN)):
-        raise ValueError("body: a contiguous (%d, %d) float64 tensor on %s expected"
-                         % (batch, FORCE_BODY_LEN, like.device))
-    return body
+    check_row(row, FORCE_BODY_LEN, ForceBody, lib().qloco_force_body_check,
+              lambda: "qloco_force_body_check refuses the row")
 
 
 def hw_torque_ff(Jaco, grf_opt, grf_base, dynamic_count, stream=None):
@@ -200,7 +169,7 @@ class ForceQP:
              FT_total_des, mode, right_support, y_coef, body=None):
         """servo.cpp:1224-1228: force_distribution(...) then force_opt(...).
         body: (B, 16) float64 device rows of force_body_rows, one per robot."""
-        body = _body_arg(body, self.batch, self.F_leg_ref)
+        body = rows_arg(body, self.batch, FORCE_BODY_LEN, self.grf_opt.dtype, self.grf_opt.device)
         check(lib().qloco_force_qp_solve_body(
             C.byref(self.params), self.batch, ptr(com_des), ptr(leg_des), ptr(F_force_des),
             ptr(rfoot_des), ptr(lfoot_des), ptr(base_p), ptr(feet_p), ptr(FT_total_des),
@@ -281,7 +250,7 @@ class ServoForceBlock:
              gait_mode, y_offset, loop_count, Jaco, foot_rel_mea, v_est_rel, body=None):
         """body: (B, 16) float64 device rows of force_body_rows, one per robot."""
         o = self.out
-        body = _body_arg(body, self.batch, o["tau"])
+        body = rows_arg(body, self.batch, FORCE_BODY_LEN, o["tau"].dtype, o["tau"].device)
         check(lib().qloco_servo_force_block_body(
             C.byref(self.params), self.batch, ptr(self.ws), ptr(coma_des), ptr(com_des),
             ptr(rfoot_des), ptr(lfoot_des), ptr(body_p_des), ptr(foot_des), ptr(right_support),

@@ -19,6 +19,7 @@ from dataclasses import dataclass
 import numpy as np
 
 from ._lib import SrbdModel, SrbdSpec, check, lib, ptr
+from ._rows import build_rows
 
 GAITS = {"trot": 0, "pace": 1, "biped": 1, "mixed": 2, "stance": 3}
 PLACE_STATES = 8  # placement states a BatchedConvexMpc keeps (one per batch, device, stream)
@@ -117,24 +118,16 @@ def model_rows(batch, spec=None, **columns):
     values (or 3 x 3, read col-major) for every robot or (B, 9).  Edit single
     rows in place, then move the array to the device
     (torch.from_numpy(rows).to(dev))."""
-    B = int(batch)
-    rows = np.zeros((B, 16), np.float32)
     sp = spec if spec is not None else default_spec()
-    check(lib().qloco_srbd_model_from_spec(C.byref(sp), B, rows.ctypes.data_as(C.POINTER(SrbdModel))),
-          "qloco_srbd_model_from_spec")
-    for name, v in columns.items():
-        if name not in MODEL_COLUMNS:
-            raise ValueError("model_rows: unknown column %r (one of %s)" % (name, sorted(MODEL_COLUMNS)))
-        lo, hi = MODEL_COLUMNS[name]
-        a = np.asarray(v, dtype=np.float32)
-        if name == "inertia":
-            if a.shape == (3, 3):
-                a = a.T.reshape(9)  # col-major
-            a = np.broadcast_to(a.reshape(-1, 9), (B, 9))
-        else:
-            a = np.broadcast_to(a.reshape(-1, 1), (B, 1))
-        rows[:, lo:hi] = a
-    return rows
+    fill = lambda B, rows: check(lib().qloco_srbd_model_from_spec(
+        C.byref(sp), B, rows.ctypes.data_as(C.POINTER(SrbdModel))), "qloco_srbd_model_from_spec")
+
+    def whole_rows(name, a, width):
+        if name == "inertia" and a.shape == (3, 3):
+            a = a.T.reshape(9)  # col-major
+        return a.reshape(-1, width)  # whole rows only: a scalar inertia does not broadcast
+
+    return build_rows(batch, 16, np.float32, MODEL_COLUMNS, fill, columns, "model_rows", whole_rows)
 
 
 @dataclass

@@ -19,12 +19,12 @@ tests/test_a1_ctrl.py checks that the figures reproduce); the kernel is a
 third formulation, so each bound is 16 x the measured spread.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import a1_ctrl_ref as R
+import host_exe
 from quadrupedal_loco_amd import a1ctrl
 
 torch = pytest.importorskip("torch")
@@ -356,8 +356,4 @@ def test_a1_tick_forces_are_the_qp_solution_of_its_own_state():
 
 def test_a1_ctrl_cpp_shim_matches_c_abi():
     _dev()
-    exe = os.path.join(ROOT, "tests", "cpp", "_build", "test_a1_ctrl_host")
-    assert os.path.exists(exe), "run __graft_entry__.build()"
-    r = subprocess.run(["timeout", "-k", "10", "120", exe], capture_output=True, text=True)
-    print(r.stdout)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+    print(host_exe.run("test_a1_ctrl_host").stdout)

@@ -108,7 +108,7 @@ def test_a1_est_cpp_shim_exported():
     # built here when the tree's build products under tests/ are not there
     # (build.py skips the compile when the program is up to date)
     from quadrupedal_loco_amd import build as qb
-    exe = qb.build_a1_est_host_test()
+    exe = qb.build_host_exe("test_a1_est_host")
     assert exe == os.path.join(ROOT, "tests", "cpp", "_build", "test_a1_est_host") and os.path.exists(exe)
 
 

@@ -12,7 +12,6 @@ with the restatement keeps every bound of tests/test_a1qp_gpu.py::_compare;
 the figures it prints are recorded in profiles/a1qp_body_rows_ab.txt."""
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -23,6 +22,7 @@ pytestmark = pytest.mark.gpu
 
 import a1qp_body_cases as BC  # noqa: E402
 import a1qp_cases as AC  # noqa: E402
+import host_exe  # noqa: E402
 from quadrupedal_loco_amd import a1ctrl, a1qp, srbd  # noqa: E402
 
 KEYS = BC.KEYS
@@ -335,7 +335,5 @@ def test_a1_tick_with_per_robot_bodies():
 def test_cpp_set_bodies():
     from quadrupedal_loco_amd import build
     _dev()
-    exe = build.build_a1qp_body_host_test()
-    assert os.path.exists(exe)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+    assert os.path.exists(build.build_host_exe("test_a1qp_body_host"))
+    host_exe.run("test_a1qp_body_host")

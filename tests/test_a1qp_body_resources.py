@@ -8,7 +8,7 @@ still run two waves per SIMD (64-thread workgroups: <= 256 registers),
 spill-free, without scratch, in at most 8 KB of LDS."""
 import pytest
 
-from test_kernel_resources import _kernels
+from test_kernel_resources import _kernels, assert_budget
 
 NO_ROWS = "_ZN5qloco2a112a1_qp_kernelILb0EEEvNS0_4ArgsE"
 ROWS = "_ZN5qloco2a112a1_qp_kernelILb1EEEvNS0_4ArgsE"
@@ -26,17 +26,8 @@ def test_both_instantiations_exist(kernels):
 
 
 def test_no_rows_instantiation_keeps_the_budget_it_had(kernels):
-    k = kernels[NO_ROWS]
-    assert k[".vgpr_count"] + k[".agpr_count"] <= PARENT_VGPRS, (k[".vgpr_count"], k[".agpr_count"])
-    assert k[".group_segment_fixed_size"] <= PARENT_LDS, k[".group_segment_fixed_size"]
-    assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
-    assert not k.get(".uses_dynamic_stack", False)
+    assert_budget(kernels[NO_ROWS], PARENT_VGPRS, PARENT_LDS)
 
 
 def test_rows_instantiation_runs_two_waves_per_simd(kernels):
-    k = kernels[ROWS]
-    assert k[".vgpr_count"] + k[".agpr_count"] <= 256, (k[".vgpr_count"], k[".agpr_count"])
-    assert k[".group_segment_fixed_size"] <= 8192, k[".group_segment_fixed_size"]
-    assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
-    assert not k.get(".uses_dynamic_stack", False)
-    assert k[".max_flat_workgroup_size"] == 64
+    assert_budget(kernels[ROWS], 256, 8192, workgroup=64)

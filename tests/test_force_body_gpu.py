@@ -14,7 +14,6 @@ run of a (family, launch) is computed once and shared.
 """
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -25,6 +24,7 @@ pytestmark = pytest.mark.gpu
 
 import force_body_cases as BC  # noqa: E402
 import force_cases as FC  # noqa: E402
+import host_exe  # noqa: E402
 
 from quadrupedal_loco_amd import build, go1servo, qp  # noqa: E402
 from quadrupedal_loco_amd._lib import lib  # noqa: E402
@@ -497,7 +497,5 @@ def test_cpp_set_bodies():
     """tests/cpp/test_force_body_host.cpp: set_bodies of Dynamiccclass,
     ServoForceBlock and Go1ServoBatch, and nullptr back to the params."""
     _dev()
-    exe = build.build_force_body_host_test()
-    assert os.path.exists(exe)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+    assert os.path.exists(build.build_host_exe("test_force_body_host"))
+    host_exe.run("test_force_body_host")

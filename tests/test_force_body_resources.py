@@ -10,7 +10,7 @@ must still run two waves per SIMD (64-thread workgroups: <= 256 registers),
 spill-free, without scratch, in at most 20,480 / 10,240 B of LDS."""
 import pytest
 
-from test_kernel_resources import FORCE_GW16, FORCE_GW8, _kernels
+from test_kernel_resources import FORCE_GW16, FORCE_GW8, _kernels, assert_budget
 
 ROWS_GW8 = "_ZN5qloco20force_qp_body_kernelILi8EEEvNS_9ForceArgsEPK16qloco_force_body"
 ROWS_GW16 = "_ZN5qloco20force_qp_body_kernelILi16EEEvNS_9ForceArgsEPK16qloco_force_body"
@@ -31,22 +31,12 @@ def test_the_four_kernels_exist(kernels):
 
 @pytest.mark.parametrize("name", sorted(PARENT))
 def test_no_rows_kernels_keep_the_budget_they_had(kernels, name):
-    k = kernels[name]
-    vgprs, lds = PARENT[name]
-    assert k[".vgpr_count"] + k[".agpr_count"] <= vgprs, (k[".vgpr_count"], k[".agpr_count"])
-    assert k[".group_segment_fixed_size"] <= lds, k[".group_segment_fixed_size"]
-    assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
-    assert not k.get(".uses_dynamic_stack", False)
+    assert_budget(kernels[name], *PARENT[name])
 
 
 @pytest.mark.parametrize("name", sorted(ROWS_LDS))
 def test_rows_kernels_run_two_waves_per_simd(kernels, name):
-    k = kernels[name]
-    assert k[".vgpr_count"] + k[".agpr_count"] <= 256, (k[".vgpr_count"], k[".agpr_count"])
-    assert k[".group_segment_fixed_size"] <= ROWS_LDS[name], k[".group_segment_fixed_size"]
-    assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0
-    assert not k.get(".uses_dynamic_stack", False)
-    assert k[".max_flat_workgroup_size"] == 64
+    assert_budget(kernels[name], 256, ROWS_LDS[name], workgroup=64)
 
 
 def test_the_servo_kernels_and_the_mark_pass_are_spill_free(kernels):

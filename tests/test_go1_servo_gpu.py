@@ -24,7 +24,6 @@ its threshold).
 """
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -34,6 +33,7 @@ torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 import go1_servo_ref as K  # noqa: E402
+import host_exe  # noqa: E402
 
 from quadrupedal_loco_amd import go1servo, kin  # noqa: E402
 from quadrupedal_loco_amd._lib import GO1_SERVO_DIAG  # noqa: E402
@@ -334,17 +334,11 @@ def test_ctrl_msg_feeds_the_rt_node():
     assert float(o.ctrl_msg[0, 0]) == 2.0
 
 
-EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_go1_servo_host")
-
-
 def test_cpp_shim_matches_python_path():
     """qloco::Go1ServoBatch for B = 3 over 20 ticks: q_cmd, the state row, the
     torques, grf_opt, the four angle_des and the go1_gait_data row are the
     Python path's bits."""
     _dev()
-    if not os.path.exists(EXE):
-        from quadrupedal_loco_amd import build as qb
-        qb.build()
     B, ticks = 3, 20
     inp = _inputs(B)
     hx = lambda a: " ".join(float(x).hex() for x in np.ravel(a))
@@ -353,9 +347,8 @@ def test_cpp_shim_matches_python_path():
         for b in range(B):
             lines.append(" ".join([hx(inp["q_mea"][t, b]), hx(inp["quat"][t, b]), hx(inp["gait_msg"][t, b])]))
     p = K.TEST_PARAMS
-    r = subprocess.run([EXE, str(B), str(ticks), repr(p["stand_duration"]), repr(p["t_walk_start"]),
-                        repr(p["t_period"])], input="\n".join(lines), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    r = host_exe.run("test_go1_servo_host", [B, ticks, repr(p["stand_duration"]), repr(p["t_walk_start"]),
+                                             repr(p["t_period"])], input="\n".join(lines))
     rows = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("T ")]
     assert len(rows) == ticks * B
     g = _run(B, False)

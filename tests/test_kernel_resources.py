@@ -85,6 +85,17 @@ def kernels():
     return _kernels()
 
 
+def assert_budget(k, vgprs, lds=None, workgroup=None):
+    """Kernel `k` of _kernels(): at most `vgprs` registers (AGPRs included) and `lds` bytes of LDS,
+    no scratch, no spills, no dynamic stack and, if given, that flat workgroup size."""
+    name = k[".name"]
+    assert k[".vgpr_count"] + k[".agpr_count"] <= vgprs, (name, k[".vgpr_count"], k[".agpr_count"])
+    assert lds is None or k[".group_segment_fixed_size"] <= lds, (name, k[".group_segment_fixed_size"])
+    assert k[".private_segment_fixed_size"] == 0 and k[".vgpr_spill_count"] == 0, name
+    assert not k.get(".uses_dynamic_stack", False), name
+    assert workgroup is None or k[".max_flat_workgroup_size"] == workgroup, name
+
+
 def test_every_kernel_is_gfx950_and_listed(kernels):
     assert len(kernels) >= 30
     for name in list(SPILL_BOUND) + FOUR_WAVE + TWO_WAVE + NO_SCRATCH:
@@ -114,10 +125,7 @@ def test_two_wave_literal_kernel_budget(kernels):
     """The two-wave literal kernel: <= 256 registers (two waves
     per SIMD), LDS for four workgroups per CU, spill-free."""
     for name in TWO_WAVE:
-        k = kernels[name]
-        assert k[".vgpr_count"] + k[".agpr_count"] <= 256, (name, k[".vgpr_count"])
-        assert k[".group_segment_fixed_size"] <= 40960, (name, k[".group_segment_fixed_size"])
-        assert k[".vgpr_spill_count"] == 0 and k[".private_segment_fixed_size"] == 0, name
+        assert_budget(kernels[name], 256, 40960)
 
 
 # the force QP (DESIGN.md §4): 8-lane groups (grouped launch) and 16-lane
@@ -129,7 +137,5 @@ FORCE_GW16 = "_ZN5qloco15force_qp_kernelILi16EEEvNS_9ForceArgsE"
 
 def test_force_qp_kernel_budget(kernels):
     for name in (FORCE_GW8, FORCE_GW16):
-        k = kernels[name]
-        assert k[".vgpr_count"] + k[".agpr_count"] <= 256, (name, k[".vgpr_count"])
-        assert k[".vgpr_spill_count"] == 0 and k[".private_segment_fixed_size"] == 0, name
+        assert_budget(kernels[name], 256)
     assert 6 * kernels[FORCE_GW8][".group_segment_fixed_size"] <= 160 * 1024

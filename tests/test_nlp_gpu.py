@@ -15,11 +15,11 @@ reproduce); the kernel is a third formulation, so each bound is 16 x the
 measured spread of that key (the convention of tests/test_a1_ctrl_gpu.py).
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_exe
 import nlp_ref as R
 import oracle_lib as O
 
@@ -282,23 +282,16 @@ def test_tick_chains_into_support_phase():
     assert checked >= 0.9 * B * len(range(0, T, 3))
 
 
-EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_nlp_host")
-
-
 def test_cpp_shim_matches_python_path(tmp_path):
     """qloco::NLPStepTimingBatch::step_timing_opti_loop for B = 1: the filled
     slots of the 38-vector are the Python path's bits, the listed ones NaN."""
     _dev()
-    if not os.path.exists(EXE):
-        from quadrupedal_loco_amd import build as qb
-        qb.build()
     ticks = 40
     sl, sw = 0.075, 2 * 0.12675
     inp = R.tick_inputs(41, 1, ticks)
-    r = subprocess.run([EXE, str(ticks)], input="\n".join(
+    r = host_exe.run("test_nlp_host", [ticks], input="\n".join(
         " ".join(repr(float(x)) for x in np.concatenate([inp["est"][t, 0], inp["rfoot"][t, 0], inp["lfoot"][t, 0]]))
-        for t in range(ticks)), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stdout + r.stderr
+        for t in range(ticks)))
     rows = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("T ")]
     assert len(rows) == ticks
     got = np.array([[float.fromhex(x) if x not in ("nan", "-nan") else np.nan for x in row[1:]] for row in rows])

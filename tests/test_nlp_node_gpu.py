@@ -16,12 +16,12 @@ tick is left out.
 """
 import copy
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import go1_servo_ref as G
+import host_exe
 import nlp_node_ref as N
 import nlp_ref as R
 import nlp_tick_ref as K
@@ -449,22 +449,15 @@ def test_stream_order():
         assert _same(x.cpu().numpy(), y.cpu().numpy())
 
 
-EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_nlp_node_host")
-
-
 def test_cpp_shim_matches_python_path():
     """qloco::NLPRTControlBatch for B = 1 through one not-started tick, the
     squat and 12 walking ticks on stepped ground: every row is the Python
     path's bits."""
-    if not os.path.exists(EXE):
-        from quadrupedal_loco_amd import build as qb
-        qb.build()
     ticks, sh = LEAD + 12, 0.02
     ids = [7]
     msgs = [_msg(ids, n, 0.0 if n == 0 else 1.0)[0] for n in range(ticks)]
-    r = subprocess.run([EXE, str(ticks), repr(sh)], input="\n".join(
-        " ".join(repr(float(x)) for x in m) for m in msgs), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+    r = host_exe.run("test_nlp_node_host", [ticks, repr(sh)], input="\n".join(
+        " ".join(repr(float(x)) for x in m) for m in msgs))
     rows = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("T ")]
     assert len(rows) == ticks
     node = nlp.PlannerNode(1, _dev(), steplength=0.075, stepwidth=2 * HW, stepheight=sh)

@@ -17,11 +17,11 @@ at 16 x max(pooled median, that tick's own A - B difference), see
 nlp_tick_ref.PER_TICK_KEYS.  No robot and no tick is left out.
 """
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_exe
 import nlp_ref as R
 import nlp_tick_ref as K
 
@@ -291,23 +291,16 @@ def test_tick_state_round_trip():
     assert np.array_equal(pl.get_state().cpu().numpy(), before)          # the first record is another workspace
 
 
-EXE = os.path.join(ROOT, "tests", "cpp", "_build", "test_nlp_tick_host")
-
-
 def test_cpp_shim_matches_python_path():
     """qloco::NLPClassBatch for B = 1 over the first 12 ticks on stepped
     ground: the 38-vector, the 18-vector and right_support are the Python
     path's bits."""
     _dev()
-    if not os.path.exists(EXE):
-        from quadrupedal_loco_amd import build as qb
-        qb.build()
     ticks, sh = 12, 0.02
     inp = R.tick_inputs(41, 1, ticks)
-    r = subprocess.run([EXE, str(ticks), repr(sh)], input="\n".join(
+    r = host_exe.run("test_nlp_tick_host", [ticks, repr(sh)], input="\n".join(
         " ".join(repr(float(x)) for x in np.concatenate([inp["est"][t, 0], inp["rfoot"][t, 0], inp["lfoot"][t, 0]]))
-        for t in range(ticks)), capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+        for t in range(ticks)))
     rows = [ln.split() for ln in r.stdout.splitlines() if ln.startswith("T ")]
     assert len(rows) == ticks
     pl = nlp.PlannerTick(1, _dev(), steplength=0.075, stepwidth=2 * 0.12675, stepheight=sh)

@@ -24,7 +24,6 @@ The uniform calls are computed once per case, shared and read-only."""
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -33,6 +32,7 @@ torch = pytest.importorskip("torch")
 
 pytestmark = pytest.mark.gpu
 
+import host_exe  # noqa: E402
 import oracle_lib as O  # noqa: E402
 from srbd_ref import Instance, np_build  # noqa: E402
 from test_srbd_gpu import SEED, U0Bound, _dev  # noqa: E402
@@ -441,7 +441,5 @@ def test_handle_world1_with_rows_matches_single_gpu_solve(mode, gait):
 def test_cpp_set_models():
     from quadrupedal_loco_amd import build
     _dev()
-    exe = build.build_srbd_model_host_test()
-    assert os.path.exists(exe)
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ALL OK" in r.stdout, r.stdout + r.stderr
+    assert os.path.exists(build.build_host_exe("test_srbd_model_host"))
+    host_exe.run("test_srbd_model_host")
